@@ -1,8 +1,23 @@
 """Benchmark: utterances/s of the MFCC + BiGRU train step on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
                     [--model mfcc_bgru|fbanks_cnn|resnet_bgru|spec_bgru|mfrn_bgru|cnn_bgru|spec_cnn]
                     [--batch B]
+
+A plain run does only what the headline figure needs: it sets up, runs W warm-up steps, times K steps,
+writes the outputs of the last timed step when --dump-outputs is given, and prints the result line
+("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", the config).  Everything else
+described below — the per-kernel eager pass behind "kernels" / "roofline", the bf16 re-timing, "configs",
+"h2d", the feature rooflines and the CPU baseline — runs only with --full (where the --no-* options
+still switch single parts off).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned to its
+caller as DIR/<name>.npy (float32): "loss" (the step's loss, shape [1]) and "logits" (the model's
+outputs on that step's batch, [B, classes]; an array of more than DUMP_MAX_ELEMS elements would be
+written as a fixed, seeded sample of its elements, sorted indices from numpy's default_rng(0)).
+Weights, clips and labels are seeded and the kernels are deterministic, so two runs with the same
+arguments start from identical inputs and write identical arrays (measured bit for bit on cfg2 at
+batch 256 and 64, cfg3 and cfg5 fp16, two processes each).
 
 --model selects the BASELINE.json config (default = configs[1], the metric's headline model):
   mfcc_bgru   cfg2: on-device MFCC[39x51] + model_mfcc_bgru, 256 clips per GPU
@@ -46,7 +61,7 @@ The per-kernel HIP-event timers cannot run inside a graph: kernel times ("kernel
 come from a separate eager pass of the same step (--prof-steps, default 5), reported with its own
 "eager_ms_per_step".
 
-Default run (no --model): the cfg2 headline, then compact records under "configs" for BASELINE.json's
+--full without --model: the cfg2 headline, then compact records under "configs" for BASELINE.json's
 other configs at their per-GPU batch — cfg3 fbanks_cnn fp32 512, cfg4 resnet_bgru fp32 512, cfg5
 spec_bgru fp16 512 with the noise-mix in the step (static loss scale 1024 with the overflow check and
 skip) — and the metric's literal MFCC+CNN-BiGRU model (mfrn_bgru fp32 256), each with value /
@@ -54,7 +69,7 @@ ms_per_step / roofline (--no-configs skips them); "h2d": the cfg2 step (fp32 and
 pinned host memory with a double-buffered upload (SURVEY.md §8d's second figure; --no-h2d skips it);
 "feature_roofline_other": K2 (fbank) and K3 (spectrogram) alone on 65,536 clips.
 
-Measurement extras on the same line:
+Measurement extras on the same line (--full):
   roofline     — the dominant kernel of the timed steps, timed live with HIP events on its launch
                  stream (srk_prof_*), algorithmic flops / avg launch time vs the MFMA peak of its
                  operand type (fp32 157.3 TF, bf16/fp16 2.5 PF dense);
@@ -87,6 +102,7 @@ PEAK_LP_MFMA_TFLOPS = 2500.0      # MI355X_MICROARCH.md, dense bf16 / fp16 MFMA 
 FP16_LOSS_SCALE = 1024.0          # static loss scale of the fp16 mode (optim.LossScaler: unscaled in the Adam
                                   # kernel, a step with inf / NaN gradients skipped and counted)
 PEAK_HBM_GBS = 8000.0             # MI355X HBM3E spec
+DUMP_MAX_ELEMS = 8 * 1024 * 1024  # --dump-outputs: per-array cap (32 MB of float32; loss + logits < 64 MB)
 MFCC_BYTES_PER_CLIP = 71956       # 64,000 in + 7,956 out
 # FlopCounterMode on the reference modules (cnn_bgru / spec_cnn: on the oracle restatements)
 TRAIN_GFLOP_PER_UTT = {"mfcc_bgru": 1.9434, "fbanks_cnn": 2.1449, "resnet_bgru": 25.8191,
@@ -410,7 +426,7 @@ class Workload:
         out = self.model(self._inputs(srcs))
         loss = self.crit(out, lab)
         (self.scaler.scale(loss) if self.scaler is not None else loss).backward()
-        return loss
+        return loss, out.detach()
 
     def _exchange_and_update(self):
         if self.reducer is not None:
@@ -420,18 +436,18 @@ class Workload:
         self.opt.step(scaler=self.scaler)
 
     def eager_step(self, i):
-        loss = self._fwd_bwd(self._batch(i), self.lab[i % self.args.pool])
+        res = self._fwd_bwd(self._batch(i), self.lab[i % self.args.pool])
         self._exchange_and_update()
-        return loss
+        return res
 
     def _graph_body(self):
         j = self._slot
-        loss = self._fwd_bwd(self._batch(j), self.lab[j])
+        res = self._fwd_bwd(self._batch(j), self.lab[j])
         if self.world == 1:
             self.opt.step(scaler=self.scaler)
         elif self.exchange_in_graph:
             self._exchange_and_update()   # the bucketed RCCL all-reduces + Adam, captured with the step
-        return loss
+        return res
 
     def _capture(self, graph, warmup):
         """One GraphedStep per pre-staged batch slot, sharing one memory pool."""
@@ -444,8 +460,18 @@ class Workload:
                                       pool=graphs[0].pool() if graphs else None, capture_error_mode=mode))
         return graphs
 
-    def run(self, precision, steps, warmup, graph):
-        """W warm-up + K timed steps at one matrix precision -> record dict (rank 0 uses it)."""
+    def _dump(self, path, loss, logits):
+        """--dump-outputs: what the last timed step handed its caller, as float32 .npy files."""
+        os.makedirs(path, exist_ok=True)
+        for name, t in (("loss", loss.detach().reshape(1)), ("logits", logits)):
+            if t.numel() > DUMP_MAX_ELEMS:
+                idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+                t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+    def run(self, precision, steps, warmup, graph, dump=None):
+        """W warm-up + K timed steps at one matrix precision -> record dict (rank 0 uses it); `dump`:
+        the --dump-outputs directory (rank 0 writes the last timed step's outputs there)."""
         args = self.args
         log("bench: %s %s B=%d, %d warm-up + %d timed steps%s" % (self.name, precision, self.B, warmup, steps,
                                                                    " (HIP graph)" if graph else ""))
@@ -490,10 +516,10 @@ class Workload:
                     graphs = self._capture(graph, warmup)
             self.graph_allreduce = "in graph" if self.exchange_in_graph else "eager after replay"
             for g in graphs:
-                loss = g.replay()    # one untimed replay of each: every captured step runs once before timing
+                loss, logits = g.replay()    # one untimed replay of each: every captured step runs once before timing
         else:
             for i in range(warmup):
-                loss = self.eager_step(i)
+                loss, logits = self.eager_step(i)
         torch.cuda.synchronize()
         if not torch.isfinite(loss).item():
             raise SystemExit("non-finite loss during warm-up")
@@ -506,11 +532,11 @@ class Workload:
         t0 = time.perf_counter()
         for i in range(steps):
             if graphs:
-                loss = graphs[i % args.pool].replay()
+                loss, logits = graphs[i % args.pool].replay()
                 if self.world > 1 and not self.exchange_in_graph:
                     self._exchange_and_update()
             else:
-                loss = self.eager_step(i)
+                loss, logits = self.eager_step(i)
         torch.cuda.synchronize()
         if self.world > 1:
             torch.distributed.barrier()
@@ -520,6 +546,8 @@ class Workload:
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
             el = float(t.item())
         final_loss = float(loss.item())
+        if dump and self.rank == 0:
+            self._dump(dump, loss, logits)
         for g in graphs:
             g.release()
         del graphs
@@ -696,6 +724,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed step's outputs (loss, logits) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the per-kernel eager pass (kernels, "
+                         "roofline), the bf16 re-timing, the other configs, h2d, the feature rooflines and the CPU "
+                         "baseline (each still switched off by its --no-* option)")
     ap.add_argument("--batch", type=int, default=None, help="clips per GPU per step (default per model)")
     ap.add_argument("--model", default=None, help="default: mfcc_bgru (cfg2) + the other configs under \"configs\"")
     ap.add_argument("--pool", type=int, default=4, help="distinct pre-staged batches per rank")
@@ -734,6 +769,9 @@ def main():
     ap.add_argument("--cpu-plumbing", action="store_true",
                     help="exercise the N-rank launch / timing / JSON path over gloo on CPU (no GPU; no measurement)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: set up, warm up, time the steps, print the headline line
+        args.lowprec = args.h2d = args.configs = False
+        args.no_prof = args.no_feature_roofline = args.no_cpu_baseline = True
     default_run = args.model is None
     args.model = args.model or "mfcc_bgru"
     if args.model not in DEFAULT_BATCH:
@@ -753,7 +791,7 @@ def main():
     torch.cuda.set_device(dev)
     B = args.batch or DEFAULT_BATCH[args.model]
     wl = Workload(args, args.model, B, rank, world, dev)
-    main_rec = wl.run(args.precision, args.steps, args.warmup, args.graph)
+    main_rec = wl.run(args.precision, args.steps, args.warmup, args.graph, dump=args.dump_outputs)
     # the same step with 16-bit matrix-core operands (BASELINE.json cfg2 names bf16), same line
     lp_rec = None
     if args.lowprec and args.precision == "fp32":
@@ -815,6 +853,9 @@ def main():
                           % (main_rec["prof_steps"], main_rec["eager_ms"])) if main_rec["eager_ms"] else
                          "the timed steps, HIP events on the launch stream",
     }
+    if not args.full:   # a plain run takes no kernel timings
+        for k in ("roofline", "kernels", "kernel_timing"):
+            del res[k]
     if lp_rec is not None:
         res["bf16"] = {"dtype": "bf16", "value": round(world * B * args.steps / lp_rec["el"], 2),
                        "ms_per_step": round(lp_rec["el"] / args.steps * 1e3, 3),

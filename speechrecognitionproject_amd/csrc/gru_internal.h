@@ -10,7 +10,7 @@ namespace srk {
 // Arrival counters / per-producer flags of the persistent kernels ([2 directions][groups <= 4] at a
 // 64-B stride, or [2][G][32] flags: words 0..255; the fp32 two-chain kernels' per-wave flags
 // [2 dir][G][2 chains][2 row blocks][32 slices][2 k halves]: words 0..2047), the XCD census in
-// words kCensusOff..+8; zeroed by a hipMemsetAsync of exactly this block before every launch.
+// words kCensusOff..+8; zeroed by zero_counters_kernel over exactly this block before every launch.
 constexpr int kCounterFloats = 4096;
 constexpr int kCensusOff = 4080;
 // Word indices of the step-ordering state inside that block — host + device, so the kernels and

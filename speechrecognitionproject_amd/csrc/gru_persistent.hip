@@ -2386,6 +2386,15 @@ int gru_bias_part_rows(int64_t B) {
   return (prec != kPrecF32 && g_opt_gru_lp2) ? kRows2 : kRows;
 }
 
+// Zeroes the kCounterFloats flag / counter words before a launch.  A kernel, not hipMemsetAsync: as a
+// memset node of a captured HIP graph the clear was not reliably visible to the agent-scope flag loads
+// of the launch behind it, and a replay then took stale flags of the previous launch for arrivals
+// (measured: the same replay from the same state gave logits differing by up to 1e-4; eager steps did not).
+__global__ void __launch_bounds__(256) zero_counters_kernel(unsigned* __restrict__ p, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) __hip_atomic_store(p + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 int gru_persistent_launch(GruPArgs a, bool backward, hipStream_t s) {
   const int gmax = gru_persistent_groups(a.H);
   SRK_REQUIRE(gmax > 0 && a.H == 512, SRK_ERR_INVALID, "gru persistent: unsupported H");
@@ -2420,7 +2429,8 @@ int gru_persistent_launch(GruPArgs a, bool backward, hipStream_t s) {
     ac.b_end = std::min(a.B, c0 + rows_per_launch);
     ac.G = (ac.b_end - c0 + rows_g - 1) / rows_g;
     ac.chunk = c0 / rows_per_launch;
-    SRK_CHECK_HIP(hipMemsetAsync(ac.counters, 0, (size_t)kCounterFloats * 4, s));
+    hipLaunchKernelGGL(zero_counters_kernel, dim3((kCounterFloats + 255) / 256), dim3(256), 0, s, ac.counters,
+                       (int)kCounterFloats);
     const dim3 grid((unsigned)(2 * ac.G * slices));
     const double flops = 2.0 * 2.0 * (double)(ac.b_end - c0) * 3 * a.H * a.H * (a.T - 1);
     ProfScope prof(backward ? (prec == kPrecF32 ? "gru_bwd_seq" : "gru_bwd_seq_lp")

@@ -144,3 +144,41 @@ def test_graph_refuses_replay_after_scratch_regrowth(gpu):
         g.replay()
     g2 = GraphedStep(body, warmup=2)
     assert g2.replay().item() == want
+
+
+def test_graph_replay_reproduces_itself(gpu):
+    """The same replay from the same restored state gives the same logits, loss and gradients bit for bit,
+    also right behind another replay (the persistent GRU's flag words are cleared by a kernel: cleared by a
+    memset node of the captured graph, a replay could take stale flags of the previous launch for arrivals
+    and read hidden-state rows of that launch, logits off by up to 1e-4).  B = 256: the full 256-workgroup grid."""
+    torch.manual_seed(0)
+    net, flat, opt, pcm, lab = _setup("mfcc_bgru", 256, seed=23)
+    crit = snn.CrossEntropyLoss()
+    out = {}
+
+    def body():
+        opt.zero_grad()
+        out["logits"] = net(pcm[0])
+        loss = crit(out["logits"], lab[0])
+        loss.backward()
+        opt.step()
+        return loss, out["logits"].detach()
+
+    g = GraphedStep(body, warmup=2)
+    out.clear()
+    state = [t.clone() for t in (flat.data, opt.exp_avg, opt.exp_avg_sq, opt.state_dev)]
+    runs = []
+    for r in range(4):
+        for t, v in zip((flat.data, opt.exp_avg, opt.exp_avg_sq, opt.state_dev), state):
+            t.copy_(v)
+        if r >= 2:          # back to back behind another replay, as a training loop runs them
+            g.replay()
+            for t, v in zip((flat.data, opt.exp_avg, opt.exp_avg_sq, opt.state_dev), state):
+                t.copy_(v)
+        loss, logits = g.replay()
+        torch.cuda.synchronize()
+        runs.append((loss.clone(), logits.clone(), flat.grad.clone(), flat.data.clone()))
+    g.release()
+    for r in runs[1:]:
+        assert all(torch.equal(a, b) for a, b in zip(r, runs[0]))
+    assert _lib.spin_timeouts() == 0

@@ -13,7 +13,7 @@ ROOT=$(pwd)
 stats() {   # stats NAME ARGS...
   local name=$1; shift
   timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$ROOT/$OUT/stats_${name}" -o run -- \
-    python3 bench.py --no-cpu-baseline --no-configs --no-feature-roofline --no-h2d "$@" \
+    python3 bench.py --full --no-cpu-baseline --no-configs --no-feature-roofline --no-h2d "$@" \
     > "$OUT/stats_${name}.json" 2> "$OUT/stats_${name}.err" \
   && python3 tools/rocpd_summary.py "$OUT/stats_${name}" > "$OUT/summary_${name}_stats.txt" && rm -rf "$OUT/stats_${name}"
 }

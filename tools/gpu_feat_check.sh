@@ -12,7 +12,7 @@ timeout -k 10 600 python -u -m pytest tests/test_features_gpu.py tests/test_mode
 rc=$?
 echo "pytest rc=$rc: $(tail -1 $OUT/pytest.log)"
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-configs --no-h2d --no-prof --no-lowprec \
+timeout -k 10 300 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-configs --no-h2d --no-prof --no-lowprec \
   > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
 python3 -c "
 import json

@@ -16,7 +16,7 @@ echo "pytest rc=$rc: $(tail -1 $OUT/pytest.log)"
 [ $rc -eq 0 ] || exit $rc
 line() {   # line NAME ARGS...
   local name=$1; shift
-  timeout -k 10 300 python bench.py --no-cpu-baseline --no-configs --no-feature-roofline --no-h2d "$@" \
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-configs --no-feature-roofline --no-h2d "$@" \
     > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err" || return $?
   python3 -c "
 import json

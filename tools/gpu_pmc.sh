@@ -15,7 +15,7 @@ ROOT=$(pwd)
 pmc() {   # pmc NAME COUNTER ARGS...
   local name=$1 ctr=$2; shift 2
   timeout -s KILL 240 rocprofv3 --kernel-trace --pmc $ctr -d "$ROOT/$OUT/pmc_${name}_${ctr}" -o run -- \
-    python3 bench.py --no-cpu-baseline --no-prof --no-configs --no-feature-roofline --no-h2d --no-graph "$@" \
+    python3 bench.py --full --no-cpu-baseline --no-prof --no-configs --no-feature-roofline --no-h2d --no-graph "$@" \
     > "$OUT/pmc_${name}_${ctr}.json" 2> "$OUT/pmc_${name}_${ctr}.err" && echo "pmc $name $ctr ok"
 }
 traffic() {   # traffic NAME MODEL BATCH PRECISIONS [--merge]

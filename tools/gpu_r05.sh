@@ -16,7 +16,7 @@ fi
 i=0
 for args in "$@"; do
   i=$((i + 1))
-  timeout -k 10 400 python bench.py --no-cpu-baseline $args > "$OUT/bench_$i.json" 2> "$OUT/bench_$i.err" || { echo "bench $i failed"; tail -20 "$OUT/bench_$i.err"; exit 1; }
+  timeout -k 10 400 python bench.py --full --no-cpu-baseline $args > "$OUT/bench_$i.json" 2> "$OUT/bench_$i.err" || { echo "bench $i failed"; tail -20 "$OUT/bench_$i.err"; exit 1; }
   python - "$OUT/bench_$i.json" "$args" <<'PY'
 import json, sys
 r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

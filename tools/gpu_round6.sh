@@ -13,7 +13,7 @@ echo "host: $(grep -m1 'model name' /proc/cpuinfo)"
 stats() {   # stats NAME ARGS...: kernel-trace stats of one config's bench command (graph replays)
   local name=$1; shift
   timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$ROOT/$OUT/stats_${name}" -o run -- \
-    python3 bench.py --no-cpu-baseline --no-configs --no-feature-roofline --no-h2d "$@" \
+    python3 bench.py --full --no-cpu-baseline --no-configs --no-feature-roofline --no-h2d "$@" \
     > "$OUT/stats_${name}.json" 2> "$OUT/stats_${name}.err" \
   && python3 tools/rocpd_summary.py "$OUT/stats_${name}" > "$OUT/summary_${name}_stats.txt" && rm -rf "$OUT/stats_${name}"
 }
@@ -21,7 +21,7 @@ stats() {   # stats NAME ARGS...: kernel-trace stats of one config's bench comma
   && echo "pytest gpu: $(tail -1 $OUT/pytest_gpu.log 2>/dev/null)" \
   && timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 \
   && echo "smoke: $(tail -1 $OUT/smoke.log)" \
-  && timeout -k 10 400 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" \
+  && timeout -k 10 400 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" \
   && echo "bench ok" \
   && stats cfg2 && stats cfg3 --model fbanks_cnn --no-lowprec --steps 10 \
   && stats cfg4 --model resnet_bgru --no-lowprec --steps 4 && stats cfg5 --model spec_bgru --precision fp16 --steps 20 \

@@ -10,4 +10,4 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 120 --timeout-method threa
 rc=$?
 tail -1 "$OUT/pytest.log"
 if [ $rc -ne 0 ]; then grep -E "^(FAILED|ERROR)|^E " "$OUT/pytest.log" | head -40; exit $rc; fi
-timeout -k 10 300 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" && cat "$OUT/bench.json"
+timeout -k 10 300 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" && cat "$OUT/bench.json"
