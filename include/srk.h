@@ -118,6 +118,22 @@ int srk_fbank_fwd_i16(const int16_t* pcm, int64_t n_clips, float* out, void* str
 int srk_mfcc_fwd_i16(const int16_t* pcm, int64_t n_clips, float* out, int layout, void* stream);
 int srk_spec_fwd_i16(const int16_t* pcm, int64_t n_clips, float* out, int transposed, void* stream);
 
+/* K2-VTLP: K2 with the mel filter bank warped per clip — the vocal-tract-length perturbation of the
+ * reference's "top" fbank model, legacy/model_8/dataset_top.py:245-267 (one np.random.uniform(0.9, 1.1)
+ * per item there).  alpha: float64 [n_clips] on the device.  With m = min(alpha, 1) the 122 mel points
+ * hz[i] of model_fbanks_cnn.py:48-50 move to hz * alpha below the knee 4800 m / alpha and to
+ * 8000 - s (8000 - hz), s = (8000 - 4800 m) / (8000 - 4800 (m / alpha)), above it (:252), then
+ * bin = floor(513 hz' / 16000) (:254) and the triangles of :256-264; everything else is K2.
+ * alpha = 1 is K2's matrix.  Domain: finite alpha in [0.8, 1.25]; a clip whose alpha is outside it (or
+ * NaN) gets NaN in its whole [98, 120] output (alpha lives on the device: no host check), the other
+ * clips are unaffected.  out: [n_clips, 98, 120].                                                      */
+int srk_fbank_vtlp_fwd(const float* pcm, int64_t n_clips, const double* alpha, float* out, void* stream);
+int srk_fbank_vtlp_fwd_i16(const int16_t* pcm, int64_t n_clips, const double* alpha, float* out, void* stream);
+/* The 122 warped FFT bins of srk_fbank_vtlp_fwd for one alpha (host only, no GPU needed; the same
+ * function the kernel evaluates).  bins: int32 [122] on the host.  SRK_ERR_INVALID for an alpha outside
+ * [0.8, 1.25] (NaN included) or a null pointer.                                                        */
+int srk_vtlp_bins(double alpha, int32_t* bins);
+
 /* K4: uniform noise mix, dataset.py:183-193 (`add_noise_uniform`) with the random draws made
  * explicit: out[b, i] = (float) int16_trunc( (double)pcm[b, i] + gain[b] * (double)
  *                        bank[file_idx[b] * bank_len + offset[b] + i] ).
@@ -448,6 +464,12 @@ int srk_dropout_fwd(const float* x, int64_t n, float p, uint64_t seed, float* y,
  * model_fbanks_cnn.py:79,98).                                                                    */
 int srk_dropout_fwd_state(const float* x, int64_t n, float p, uint64_t* state, float* y, uint8_t* keep,
                           void* stream);
+/* n float64 draws from U[lo, hi) with the seed on the device (graph-replayable, as srk_dropout_fwd_state;
+ * the VTLP warp factors, legacy/model_8/dataset_top.py:251): state = uint64[2] {base, counter},
+ * seed = base + 0xD1B54A32D192ED03 * counter; out[i] = lo + (hi - lo) * u_i (two roundings) with
+ * u_i = (z >> 11) * 2^-53, z = the splitmix64 finaliser of seed + 0x9E3779B97F4A7C15 * (i + 1); then the
+ * call advances state[1].  out: float64 [n] on the device.                                      */
+int srk_uniform_f64_state(uint64_t* state, double lo, double hi, int64_t n, double* out, void* stream);
 /* y = keep ? x * scale : 0 (dropout with an explicit keep-mask; also its backward).          */
 int srk_dropout_apply(const float* x, const uint8_t* keep, int64_t n, float scale, float* y, void* stream);
 

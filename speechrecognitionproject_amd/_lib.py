@@ -46,6 +46,10 @@ _SIGS = {
     "srk_fbank_fwd_i16": [_P, _I64, _P, _P],
     "srk_mfcc_fwd_i16": [_P, _I64, _P, _I, _P],
     "srk_spec_fwd_i16": [_P, _I64, _P, _I, _P],
+    "srk_fbank_vtlp_fwd": [_P, _I64, _P, _P, _P],
+    "srk_fbank_vtlp_fwd_i16": [_P, _I64, _P, _P, _P],
+    "srk_vtlp_bins": [_D, ctypes.POINTER(ctypes.c_int32)],
+    "srk_uniform_f64_state": [_P, _D, _D, _I64, _P, _P],
     "srk_noise_mix": [_P, _P, _I64, _I64, _P, _P, _P, _I64, _P, _P],
     "srk_spec_noise_fwd": [_P, _P, _I64, _I64, _P, _P, _P, _I64, _P, _I, _P],
     "srk_augment": [_P, _I64, _P, _I64, _P, _P, _P, _P, ctypes.c_uint64, _P, _P],

@@ -62,6 +62,7 @@ constexpr int kFbChunks = 25;
 constexpr int kFbPairs = 60, kFbPairTaps = 12;     // filters (l, 119 - l); max pair width 11
 
 struct FbankTables {
+  static constexpr bool kVtlp = false;
   const double* hamming400;
   const float2* tw256;      // W256^t
   const float2* post512;    // W512^k, k = 0..256
@@ -69,21 +70,60 @@ struct FbankTables {
   const float* pair_w;      // [60][12] weights of filter a then filter b, zero padded
 };
 
+// K2-VTLP (legacy/model_8/dataset_top.py:245-267): the same front end, the mel matrix warped per clip.
+// The constant pair table gives way to the clip's 122 warped bins, computed per item from the
+// unwarped mel points and the clip's alpha.
+constexpr int kFbPoints = 122;
+struct FbankVtlpTables {
+  static constexpr bool kVtlp = true;
+  const double* hamming400;
+  const float2* tw256;
+  const float2* post512;
+  const double* hz;         // [122] unwarped mel points in Hz (model_fbanks_cnn.py:50)
+  const double* alpha;      // [n_clips] warp factors
+};
+
+// The warp of dataset_top.py:252-254 in its float64 operation order (never fused: the floor decides a
+// bin).  One function for the kernel and the host entry srk_vtlp_bins.
+struct VtlpWarp {
+  double alpha, knee, s;
+};
+__host__ __device__ inline bool vtlp_alpha_ok(double alpha) { return alpha >= 0.8 && alpha <= 1.25; }   // false for NaN
+__host__ __device__ inline VtlpWarp vtlp_warp(double alpha) {
+#pragma clang fp contract(off)
+  const double m = alpha < 1.0 ? alpha : 1.0;
+  return VtlpWarp{alpha, (4800.0 * m) / alpha, (8000.0 - 4800.0 * m) / (8000.0 - 4800.0 * (m / alpha))};
+}
+__host__ __device__ inline int vtlp_bin(double hz, const VtlpWarp& w) {
+#pragma clang fp contract(off)
+  const double hzw = hz < w.knee ? hz * w.alpha : 8000.0 - w.s * (8000.0 - hz);
+  const double b = floor((513.0 * hzw) / 16000.0);
+  return (int)fmin(fmax(b, 0.0), 256.0);   // in [0, 256] on the whole domain; the clamp guards the LDS reads
+}
+
 // 4 waves per SIMD (<= 128 VGPRs): the window and the pass-A twiddles are read from LDS tables
 // staged once per workgroup; only the small lane constants stay in registers.
-template <typename T>
+// Tab = FbankTables: K2.  Tab = FbankVtlpTables: K2-VTLP, the same code up to the power spectrum.
+template <typename T, typename Tab>
 __global__ __launch_bounds__(256, 4) void fbank_kernel(const T* __restrict__ pcm, float* __restrict__ out,
-                                                       int64_t n_clips, FbankTables t) {
+                                                       int64_t n_clips, Tab t) {
+  constexpr bool VTLP = Tab::kVtlp;
   __shared__ v2f sbuf[4][4 * 272];   // per wave: 4 frames x (16 x 17) transpose, reused for spectra / power
   __shared__ __attribute__((aligned(16))) double s_win[400];
   __shared__ v2f s_tw[16 * 16];      // W256^(j k1) at [k1][j]
   __shared__ v2f s_post[257];        // W512^k
-  __shared__ float s_pw[kFbPairs * kFbPairTaps];
+  __shared__ float s_pw[VTLP ? 1 : kFbPairs * kFbPairTaps];
+  __shared__ double s_hz[VTLP ? kFbPoints : 1];
+  __shared__ int s_bin[VTLP ? 4 : 1][128];   // per wave: the item's clip's warped bins
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int f = lane >> 4, j = lane & 15;
   for (int i = threadIdx.x; i < 400; i += 256) s_win[i] = t.hamming400[i];
   for (int i = threadIdx.x; i < 257; i += 256) s_post[i] = v2f{t.post512[i].x, t.post512[i].y};
-  for (int i = threadIdx.x; i < kFbPairs * kFbPairTaps; i += 256) s_pw[i] = t.pair_w[i];
+  if constexpr (VTLP) {
+    for (int i = threadIdx.x; i < kFbPoints; i += 256) s_hz[i] = t.hz[i];
+  } else {
+    for (int i = threadIdx.x; i < kFbPairs * kFbPairTaps; i += 256) s_pw[i] = t.pair_w[i];
+  }
   {
     const int k1 = threadIdx.x >> 4, jj = threadIdx.x & 15;
     const float2 w = t.tw256[(jj * k1) & 255];
@@ -94,8 +134,12 @@ __global__ __launch_bounds__(256, 4) void fbank_kernel(const T* __restrict__ pcm
   float* pb = reinterpret_cast<float*>(tb);   // power [4][272] after the untangle (pitch = 16 mod 32:
                                               // two frames' 16-lane stores fill the 32 banks)
   const int pl = lane < kFbPairs ? lane : 0;
-  const int4 meta = t.pair_meta[pl];
-  const float* pw = s_pw + pl * kFbPairTaps;
+  int4 meta{0, 0, 0, 0};
+  const float* pw = nullptr;
+  if constexpr (!VTLP) {
+    meta = t.pair_meta[pl];
+    pw = s_pw + pl * kFbPairTaps;
+  }
 
   const int64_t items = n_clips * kFbChunks;
   for (int64_t it = (int64_t)blockIdx.x * 4 + wave; it < items; it += (int64_t)gridDim.x * 4) {
@@ -104,6 +148,19 @@ __global__ __launch_bounds__(256, 4) void fbank_kernel(const T* __restrict__ pcm
     const int gf = 4 * c + f;                     // this lane's frame (pass A)
     const bool live = gf < 98;
     const T* __restrict__ x = pcm + clip * kPcmLen + 160 * (live ? gf : 0);
+    bool warp_ok = true;
+    if constexpr (VTLP) {
+      // the clip's 122 warped bins into the wave's own LDS: lane l evaluates points l and l + 64.  An alpha
+      // outside the domain (NaN included) is replaced by 1 here and the clip's output by NaN at the store.
+      double al = t.alpha[clip];
+      warp_ok = vtlp_alpha_ok(al);
+      al = warp_ok ? al : 1.0;
+      const VtlpWarp w = vtlp_warp(al);
+      const int i1 = min(lane + 64, kFbPoints - 1);
+      const int b0 = vtlp_bin(s_hz[lane], w), b1 = vtlp_bin(s_hz[i1], w);
+      s_bin[wave][lane] = b0;
+      if (lane + 64 < kFbPoints) s_bin[wave][lane + 64] = b1;
+    }
     // pre-emphasis (fp32, numpy's two roundings) x Hamming (fp64, :33-41), DC / Nyquist sums in fp64
     // every lane loads (dead lanes read in-clip samples) and the products are masked after: with the
     // loads under the condition the compiler serialises their waits
@@ -193,7 +250,54 @@ __global__ __launch_bounds__(256, 4) void fbank_kernel(const T* __restrict__ pcm
     }
     wave_lds_fence();
     // mel pairs (filter l and 119 - l), |X|^2 / 512 (:44, an exact power of two), eps floor, 20 log10
-    if (lane < kFbPairs) {
+    if constexpr (VTLP) {
+      if (lane < kFbPairs) {
+        float* o = out + (clip * 98 + 4 * c) * 120;
+        // filter m (0-based) has its corners at bins[m], bins[m + 1], bins[m + 2] (dataset_top.py:257-264): it
+        // rises as (k - lo) / (mid - lo) on [lo, mid) and falls as (hi - k) / (hi - mid) on [mid, hi).  The
+        // pair's taps run back to back as in K2, with run-time bounds: any support width, k <= 256.
+        const int* bw = s_bin[wave];
+        const int lo_a = bw[lane], mid_a = bw[lane + 1], hi_a = bw[lane + 2];
+        const int lo_b = bw[119 - lane], mid_b = bw[120 - lane], hi_b = bw[121 - lane];
+        const int ka = lo_a + (mid_a > lo_a ? 1 : 0);   // the rising edge's first weight is 0: skip it
+        const int kb0 = lo_b + (mid_b > lo_b ? 1 : 0);
+        const int cnt_a = max(hi_a - ka, 0), cnt_b = max(hi_b - kb0, 0);
+        const int kb = kb0 - cnt_a;                     // tap q reads bin (q < cnt_a ? ka : kb) + q
+        // 1 / width (v_rcp_f32, <= 1 ulp; exact for powers of two): a weight is within 2 ulp of the fp32
+        // rounding of the reference's float64 ratio, 2e-6 dB
+        const float ru_a = __builtin_amdgcn_rcpf((float)max(mid_a - lo_a, 1));
+        const float rd_a = __builtin_amdgcn_rcpf((float)max(hi_a - mid_a, 1));
+        const float ru_b = __builtin_amdgcn_rcpf((float)max(mid_b - lo_b, 1));
+        const float rd_b = __builtin_amdgcn_rcpf((float)max(hi_b - mid_b, 1));
+        float sa[4] = {0.f, 0.f, 0.f, 0.f}, sb[4] = {0.f, 0.f, 0.f, 0.f};
+        const int taps = cnt_a + cnt_b;
+        for (int q = 0; q < taps; ++q) {
+          const bool fa = q < cnt_a;
+          const int k = (fa ? ka : kb) + q;
+          const bool up = k < (fa ? mid_a : mid_b);
+          const int num = up ? k - (fa ? lo_a : lo_b) : (fa ? hi_a : hi_b) - k;
+          const float w = (float)num * (up ? (fa ? ru_a : ru_b) : (fa ? rd_a : rd_b));
+          const float wa = fa ? w : 0.f, wb = fa ? 0.f : w;
+          const float* pp = pb + min(k, 256);
+#pragma unroll
+          for (int ff = 0; ff < 4; ++ff) {   // a dead frame's slice holds the spectrum of zeros; it is not stored
+            const float v = pp[ff * 272];
+            sa[ff] += wa * v;
+            sb[ff] += wb * v;
+          }
+        }
+        const float nanv = __builtin_nanf("");
+#pragma unroll
+        for (int ff = 0; ff < 4; ++ff) {
+          if (4 * c + ff >= 98) break;
+          const float va = sa[ff] * (1.0f / 512.0f), vb = sb[ff] * (1.0f / 512.0f);
+          const float da = va == 0.f ? kFbEpsDb : 20.0f * fast_log10(va);
+          const float db = vb == 0.f ? kFbEpsDb : 20.0f * fast_log10(vb);
+          o[ff * 120 + lane] = warp_ok ? da : nanv;
+          o[ff * 120 + 119 - lane] = warp_ok ? db : nanv;
+        }
+      }
+    } else if (lane < kFbPairs) {
       float* o = out + (clip * 98 + 4 * c) * 120;
       // the pair's tap weights, read once per item, split into the two filters (zero elsewhere): a
       // tap is then one LDS read and two multiply-adds, no per-tap selects
@@ -827,7 +931,30 @@ int fbank_fwd(const T* pcm, int64_t n_clips, float* out, void* stream) {
   const int64_t blocks = std::min<int64_t>((items + 3) / 4, 2048);   // waves take (clip, 4-frame chunk) items
   // algorithmic bytes: the PCM in (64000 B/clip as fp32, 32000 as int16) + 47040 out
   ProfScope prof("fbank", as_stream(stream), (16000.0 * sizeof(T) + 47040.0) * (double)n_clips);
-  hipLaunchKernelGGL(fbank_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), pcm, out, n_clips, ft);
+  hipLaunchKernelGGL((fbank_kernel<T, FbankTables>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), pcm, out,
+                     n_clips, ft);
+  SRK_CHECK_HIP(hipGetLastError());
+  return SRK_OK;
+}
+
+template <typename T>
+int fbank_vtlp_fwd(const T* pcm, int64_t n_clips, const double* alpha, float* out, void* stream) {
+  SRK_REQUIRE(n_clips >= 0 && n_clips <= INT32_MAX, SRK_ERR_INVALID, "srk_fbank_vtlp_fwd: bad n_clips %lld",
+              (long long)n_clips);
+  if (n_clips == 0) return SRK_OK;
+  SRK_REQUIRE(pcm && alpha && out, SRK_ERR_INVALID, "srk_fbank_vtlp_fwd: null pointer");
+  SRK_REQUIRE((uintptr_t)pcm % (2 * sizeof(T)) == 0, SRK_ERR_INVALID, "srk_fbank_vtlp_fwd: pcm must be %d-byte aligned",
+              (int)(2 * sizeof(T)));
+  SRK_REQUIRE((uintptr_t)alpha % sizeof(double) == 0, SRK_ERR_INVALID, "srk_fbank_vtlp_fwd: alpha must be 8-byte aligned");
+  const DeviceTables* t = nullptr;
+  if (int rc = get_tables(&t)) return rc;
+  FbankVtlpTables ft{t->hamming400, t->tw256, t->post512, t->fb_hz, alpha};
+  const int64_t items = n_clips * kFbChunks;
+  const int64_t blocks = std::min<int64_t>((items + 3) / 4, 2048);
+  // algorithmic bytes: K2's + the clip's alpha
+  ProfScope prof("fbank_vtlp", as_stream(stream), (16000.0 * sizeof(T) + 47040.0 + 8.0) * (double)n_clips);
+  hipLaunchKernelGGL((fbank_kernel<T, FbankVtlpTables>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), pcm,
+                     out, n_clips, ft);
   SRK_CHECK_HIP(hipGetLastError());
   return SRK_OK;
 }
@@ -901,6 +1028,29 @@ int srk_fbank_fwd(const float* pcm, int64_t n_clips, float* out, void* stream) {
 int srk_fbank_fwd_i16(const int16_t* pcm, int64_t n_clips, float* out, void* stream) {
   SRK_API_BEGIN
   return srk::fbank_fwd(pcm, n_clips, out, stream);
+  SRK_API_END
+}
+
+int srk_fbank_vtlp_fwd(const float* pcm, int64_t n_clips, const double* alpha, float* out, void* stream) {
+  SRK_API_BEGIN
+  return srk::fbank_vtlp_fwd(pcm, n_clips, alpha, out, stream);
+  SRK_API_END
+}
+
+int srk_fbank_vtlp_fwd_i16(const int16_t* pcm, int64_t n_clips, const double* alpha, float* out, void* stream) {
+  SRK_API_BEGIN
+  return srk::fbank_vtlp_fwd(pcm, n_clips, alpha, out, stream);
+  SRK_API_END
+}
+
+int srk_vtlp_bins(double alpha, int32_t* bins) {
+  SRK_API_BEGIN
+  SRK_REQUIRE(bins, SRK_ERR_INVALID, "srk_vtlp_bins: null pointer");
+  SRK_REQUIRE(srk::vtlp_alpha_ok(alpha), SRK_ERR_INVALID, "srk_vtlp_bins: alpha %g outside [0.8, 1.25]", alpha);
+  const double* hz = srk::fbank_hz_points();
+  const srk::VtlpWarp w = srk::vtlp_warp(alpha);
+  for (int i = 0; i < srk::kFbPoints; ++i) bins[i] = srk::vtlp_bin(hz[i], w);
+  return SRK_OK;
   SRK_API_END
 }
 

@@ -158,13 +158,21 @@ int to_pairs(const std::vector<double>& w, int nf, int nbins, int taps, std::vec
   return SRK_OK;
 }
 
+// models/model_fbanks_cnn.py:48-50: the 122 mel points in Hz
+std::vector<double> fbank_hz() {
+  const int nfilt = 120, sr = 16000;
+  const double high = 2595.0 * std::log10(1.0 + (sr / 2.0) / 700.0);
+  std::vector<double> mel = linspace(0.0, high, nfilt + 2), hz(nfilt + 2);
+  for (int i = 0; i < nfilt + 2; ++i) hz[i] = 700.0 * (std::pow(10.0, mel[i] / 2595.0) - 1.0);
+  return hz;
+}
+
 // models/model_fbanks_cnn.py:46-59
 std::vector<double> fbank_matrix() {
   const int nfilt = 120, nfft = 512, sr = 16000, nb = nfft / 2 + 1;
-  const double high = 2595.0 * std::log10(1.0 + (sr / 2.0) / 700.0);
-  std::vector<double> mel = linspace(0.0, high, nfilt + 2), bin(nfilt + 2);
-  for (int i = 0; i < nfilt + 2; ++i)
-    bin[i] = std::floor((nfft + 1) * (700.0 * (std::pow(10.0, mel[i] / 2595.0) - 1.0)) / sr);
+  const std::vector<double> hz = fbank_hz();
+  std::vector<double> bin(nfilt + 2);
+  for (int i = 0; i < nfilt + 2; ++i) bin[i] = std::floor((nfft + 1) * hz[i] / sr);
   std::vector<double> fb((size_t)nfilt * nb, 0.0);
   for (int m = 1; m <= nfilt; ++m) {
     const int fl = (int)bin[m - 1], fc = (int)bin[m], fr = (int)bin[m + 1];
@@ -242,6 +250,7 @@ int build_tables(DeviceTables& t) {
     if ((rc = to_pairs(fbank_matrix(), 120, 257, 12, meta, pv)) || (rc = upload(&t.fbp_meta, meta)) ||
         (rc = upload(&t.fbp_w, pv)))
       return rc;
+    if ((rc = upload(&t.fb_hz, fbank_hz()))) return rc;
     std::vector<int> wl;
     std::vector<float> wv;
     if ((rc = to_windows(slaney_mel(), 128, 321, 16, wl, wv)) || (rc = upload(&t.mel16_lo, wl)) ||
@@ -313,6 +322,11 @@ int build_tables(DeviceTables& t) {
 }
 
 }  // namespace
+
+const double* fbank_hz_points() {
+  static const std::vector<double> hz = fbank_hz();
+  return hz.data();
+}
 
 int get_tables(const DeviceTables** out) {
   int dev = 0;

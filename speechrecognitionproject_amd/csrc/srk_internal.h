@@ -60,6 +60,7 @@ struct DeviceTables {
   // filter banks as lane pairs (filter l and nf - 1 - l, balancing narrow and wide triangles):
   // meta {lo_a, cnt_a, lo_b, cnt_b}, weights of a then b, zero padded to a fixed tap count
   int4* fbp_meta = nullptr; float* fbp_w = nullptr;     // fbank: 60 pairs x 12 taps
+  double* fb_hz = nullptr;     // [122] the fbank's unwarped mel points in Hz (K2-VTLP warps them per clip)
   float* dct = nullptr;        // [13][128] orthonormal DCT-II
   // Slaney mel as fixed 16-tap windows (zero-padded, start clamped so lo+16 <= bins)
   int* mel16_lo = nullptr; float* mel16_w = nullptr;   // [128], [128][16]
@@ -73,6 +74,8 @@ struct DeviceTables {
 
 // Returns the tables for the current HIP device, building them on first use.
 int get_tables(const DeviceTables** out);
+// The host copy of DeviceTables::fb_hz (122 doubles, built on first use; no GPU needed).
+const double* fbank_hz_points();
 
 // Matrix-core operand precision of the GEMM-shaped kernels (srk_set_option "matmul_precision"):
 // 0 = fp32 (exact fp32 MFMA, the reference's arithmetic), 1 = bf16, 2 = fp16 operands (rounded to

@@ -211,6 +211,23 @@ __global__ void dropout_state_kernel(const float* __restrict__ x, int64_t n, flo
   y[i] = k ? x[i] * scale : 0.f;
 }
 
+// U[lo, hi) in float64 from the same device state and hash as the dropout mask (53 random bits per
+// draw; lo + (hi - lo) * u in two roundings, as numpy's uniform); the counter advances behind it.
+__global__ void uniform_f64_state_kernel(const uint64_t* __restrict__ state, double lo, double hi, int64_t n,
+                                         double* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t seed = state[0] + 0xD1B54A32D192ED03ull * state[1];
+  uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((uint64_t)i + 1);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  const double u = (double)(z >> 11) * (1.0 / 9007199254740992.0);
+  const double w = (hi - lo) * u;
+  out[i] = lo + w;
+}
+
 __global__ void counter_inc_kernel(uint64_t* __restrict__ c) { c[0] += 1; }
 
 __global__ void dropout_kernel(const float* __restrict__ x, const uint8_t* __restrict__ keep, int64_t n, float scale,
@@ -334,6 +351,20 @@ int srk_dropout_fwd_state(const float* x, int64_t n, float p, uint64_t* state, f
   hipStream_t s = srk::as_stream(stream);
   hipLaunchKernelGGL(srk::dropout_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n, p,
                      1.0f / (1.0f - p), state, y, keep);
+  hipLaunchKernelGGL(srk::counter_inc_kernel, dim3(1), dim3(1), 0, s, state + 1);
+  SRK_CHECK_HIP(hipGetLastError());
+  return SRK_OK;
+  SRK_API_END
+}
+
+int srk_uniform_f64_state(uint64_t* state, double lo, double hi, int64_t n, double* out, void* stream) {
+  SRK_API_BEGIN
+  SRK_REQUIRE(n >= 0 && state && (n == 0 || out) && lo <= hi && (hi - lo) < INFINITY, SRK_ERR_INVALID,
+              "uniform_f64_state: bad args");
+  if (n == 0) return SRK_OK;
+  hipStream_t s = srk::as_stream(stream);
+  hipLaunchKernelGGL(srk::uniform_f64_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, state, lo, hi,
+                     n, out);
   hipLaunchKernelGGL(srk::counter_inc_kernel, dim3(1), dim3(1), 0, s, state + 1);
   SRK_CHECK_HIP(hipGetLastError());
   return SRK_OK;

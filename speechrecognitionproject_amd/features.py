@@ -92,12 +92,88 @@ def _entry(name, x):
     return name + "_i16" if x.dtype == torch.int16 else name
 
 
-def fbank(pcm, out=None):
-    """K2 log-mel filter banks [B, 98, 120] (models/model_fbanks_cnn.py:15-66)."""
+def fbank(pcm, alpha=None, out=None):
+    """K2 log-mel filter banks [B, 98, 120] (models/model_fbanks_cnn.py:15-66).
+
+    ``alpha``: per-clip VTLP warp factors (legacy/model_8/dataset_top.py:245-267; srk_fbank_vtlp_fwd), a
+    float64 device tensor [B] or a host sequence of B floats (uploaded).  A clip whose alpha is outside
+    [0.8, 1.25] comes back all NaN (the values live on the device: no host check)."""
     x = as_device_pcm(pcm, keep_int16=True)
     out = torch.empty((x.shape[0], 98, 120), device=x.device, dtype=torch.float32) if out is None else out
-    call(_entry("srk_fbank_fwd", x), ptr(x), x.shape[0], ptr(out), stream_ptr())
+    if alpha is None:
+        call(_entry("srk_fbank_fwd", x), ptr(x), x.shape[0], ptr(out), stream_ptr())
+        return out
+    if torch.is_tensor(alpha):
+        if alpha.dtype != torch.float64:
+            raise SrkError("fbank: alpha must be float64, got %s" % alpha.dtype)
+        a = alpha.to(x.device).contiguous()
+    else:
+        a = torch.as_tensor(alpha, dtype=torch.float64).to(x.device)
+    if a.dim() != 1 or a.numel() != x.shape[0]:
+        raise SrkError("fbank: alpha must hold one value per clip (%d), got shape %s" % (x.shape[0], tuple(a.shape)))
+    call(_entry("srk_fbank_vtlp_fwd", x), ptr(x), x.shape[0], ptr(a), ptr(out), stream_ptr())
     return out
+
+
+# VTLP draws: device index -> uint64[2] {base seed, call counter} (as int64) read and advanced by
+# srk_uniform_f64_state.  A state of its own, not nn._DROPOUT_STATE, seeded once from the device's torch
+# generator without touching its Philox offset: turning VTLP on leaves the dropout masks as they are.
+_VTLP_STATE = {}
+_VTLP_SALT = 0x56544C50A5A5A5A5   # "VTLP"
+_MASK63 = (1 << 63) - 1
+
+
+def _vtlp_state(device):
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    st = _VTLP_STATE.get(idx)
+    if st is None:
+        seed = torch.cuda.default_generators[idx].initial_seed()
+        dist = torch.distributed
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        base = ((seed * 0x9E3779B97F4A7C15) ^ (rank * 0xC2B2AE3D27D4EB4F) ^ _VTLP_SALT) & _MASK63
+        st = torch.tensor([base, 0], dtype=torch.int64, device=torch.device("cuda", idx))
+        _VTLP_STATE[idx] = st
+    return st
+
+
+def vtlp_reseed(seed, device=None):
+    """Reset the VTLP draw state of ``device`` (default: the current one): base = ``seed``, counter = 0."""
+    require_gpu()
+    idx = torch.cuda.current_device() if device is None else torch.device(device).index
+    idx = torch.cuda.current_device() if idx is None else idx
+    _VTLP_STATE[idx] = torch.tensor([int(seed) & _MASK63, 0], dtype=torch.int64, device=torch.device("cuda", idx))
+
+
+def vtlp_state(device=None):
+    """(base, counter) of the VTLP draw state (synchronizes; for tests and logs)."""
+    require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    base, counter = _vtlp_state(dev).tolist()
+    return base, counter
+
+
+def vtlp_draw(n, lo=0.9, hi=1.1, out=None):
+    """n VTLP warp factors, float64 [n] on the current device, uniform in [lo, hi)
+    (dataset_top.py:251: np.random.uniform(0.9, 1.1) per item).  Draw k of a process hashes
+    (base, k, i) on the device (srk_uniform_f64_state) and the kernel itself advances k, so an eager
+    call and a replay of a captured one are the same arithmetic."""
+    require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device()) if out is None else out.device
+    out = torch.empty(n, device=dev, dtype=torch.float64) if out is None else out
+    if out.dtype != torch.float64 or out.numel() != n or not out.is_contiguous() or out.device.type != "cuda":
+        raise SrkError("vtlp_draw: out must be a contiguous float64 device tensor of %d elements" % n)
+    if not lo <= hi:
+        raise SrkError("vtlp_draw: need lo <= hi, got %r, %r" % (lo, hi))
+    call("srk_uniform_f64_state", ptr(_vtlp_state(dev)), float(lo), float(hi), n, ptr(out), stream_ptr())
+    return out
+
+
+def vtlp_bins(alpha):
+    """The 122 FFT bins of the filter bank warped by ``alpha`` (srk_vtlp_bins: the kernel's own bin
+    function, evaluated on the host; no GPU needed) as a list of ints."""
+    bins = (ctypes.c_int32 * 122)()
+    call("srk_vtlp_bins", float(alpha), bins)
+    return list(bins)
 
 
 def mfcc(pcm, time_major=False, out=None):

@@ -21,8 +21,23 @@ def filter_banks(sample):
 
 
 class Network(nn.Module):
-    def __init__(self):
+    """``vtlp=(lo, hi)`` turns on the reference's VTLP augmentation (legacy/model_8/dataset_top.py:245-267:
+    the mel filter bank warped by one uniform(lo, hi) factor per clip) for training-mode forwards;
+    ``None`` (the default, and the reference's constructor call) never warps.  ``eval()`` never warps
+    either (dataset_top.py warps under ``self.train`` only).  The factors of the last drawn batch are in
+    ``last_alpha`` (float64 [B], one persistent buffer per batch size: a captured step reads a static
+    address)."""
+
+    def __init__(self, vtlp=None):
         super().__init__()
+        if vtlp is not None:
+            lo, hi = (float(v) for v in vtlp)
+            if not 0.8 <= lo <= hi <= 1.25:
+                raise ValueError("vtlp=(lo, hi) must satisfy 0.8 <= lo <= hi <= 1.25, got %r" % (vtlp,))
+            vtlp = (lo, hi)
+        self.vtlp = vtlp
+        self.last_alpha = None
+        self._alpha_bufs = {}
         self.conv1 = Conv2d(1, 64, kernel_size=(7, 3), padding=(3, 1))
         self.maxpool1 = MaxPool2d((1, 3))
         self.conv2 = Conv2d(64, 128, (1, 7), padding=(0, 3))
@@ -34,9 +49,21 @@ class Network(nn.Module):
         self.fc1 = Linear(512, 256)
         self.fc2 = Linear(256, 12)
 
-    def forward(self, x):
+    def _draw_alpha(self, n):
+        # one buffer per (device, batch size), kept for the module's life: a captured step of the full
+        # batch keeps its address while a short last batch runs eagerly on another
+        key = (torch.cuda.current_device(), n)
+        buf = self._alpha_bufs.get(key)
+        if buf is None:
+            buf = self._alpha_bufs[key] = torch.empty(n, device="cuda", dtype=torch.float64)
+        self.last_alpha = features.vtlp_draw(n, self.vtlp[0], self.vtlp[1], out=buf)
+        return buf
+
+    def forward(self, x, alpha=None):
         with torch.no_grad():
-            inx = features.fbank(x)                       # [B, 98, 120]
+            if alpha is None and self.training and self.vtlp is not None:
+                alpha = self._draw_alpha(x.shape[0] if len(x.shape) > 1 else 1)
+            inx = features.fbank(x, alpha=alpha)          # [B, 98, 120]
         # fused conv1 + maxpool1: NHWC [B, 98, 40, 64] (its fp32 copy skipped when conv2 reads the 16-bit one)
         h = conv1_pool(inx, self.conv1, self.maxpool1, next_conv_pool16=True)
         h = conv_pool(h, self.conv2, self.maxpool2)      # fused conv2 + maxpool2: [B, 98, 10, 128]

@@ -24,6 +24,9 @@ the device counter on top of the last eager seed, so masks (not the arithmetic) 
 ``--no-graph``.  ``--precision bf16|fp16`` runs the matrix cores on 16-bit operands (fp32
 accumulation, fp32 parameters); fp16 trains with a loss scale (``--loss-scale``: dynamic by
 default, or a fixed number) and skips any step whose gradients overflowed (optim.LossScaler).
+``--vtlp LO,HI`` (fbanks_cnn only, off by default) warps each training clip's mel filter bank by a
+factor drawn on the device (legacy/model_8/dataset_top.py:245-267); the draw's counter lives on the
+device too, so replayed and eager steps draw the same sequence.
 """
 import argparse
 import importlib
@@ -84,7 +87,22 @@ def parse(argv=None):
     p.add_argument('--save-model', action='store_true',
                    help="write model.state_dict() to OUTPUT/models/model_KEY.ckpt after training (the reference's "
                         "checkpoint path, training.py:104-107)")
-    return p.parse_args(argv)
+    p.add_argument('--vtlp', default=None, metavar='LO,HI',
+                   help="fbanks_cnn: warp each training clip's mel filter bank by a factor drawn uniformly from "
+                        "[LO, HI) (vocal-tract-length perturbation, the reference's legacy/model_8 trains with "
+                        "0.9,1.1); off by default")
+    args = p.parse_args(argv)
+    if args.vtlp is not None:
+        if args.model != 'fbanks_cnn':
+            p.error('--vtlp applies to --model fbanks_cnn only')
+        try:
+            lo, hi = (float(v) for v in args.vtlp.split(','))
+        except ValueError:
+            p.error('--vtlp takes LO,HI (two numbers), got %r' % args.vtlp)
+        if not 0.8 <= lo <= hi <= 1.25:
+            p.error('--vtlp needs 0.8 <= LO <= HI <= 1.25, got %r' % args.vtlp)
+        args.vtlp = (lo, hi)
+    return args
 
 
 def main(argv=None):
@@ -122,7 +140,10 @@ def _train(args):
             valset.reduce_dataset(args.reduce)
 
     torch.manual_seed(0)
-    model = (mod.Network() if args.mode is None else mod.Network(mode=args.mode)).to(device)
+    net_args = {} if args.mode is None else {'mode': args.mode}
+    if args.vtlp is not None:
+        net_args['vtlp'] = args.vtlp
+    model = mod.Network(**net_args).to(device)
     if args.sync_bn:
         from .nn import convert_sync_batchnorm
         model = convert_sync_batchnorm(model)
