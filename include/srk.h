@@ -278,7 +278,7 @@ int srk_gru_layer_bwd_x16(const float* x, const void* x16, int64_t B, int64_t T,
                           float* ws, void* stream);
 
 /* ---------------------------------------------------------------- K6: convolution / pooling
- * nn.Conv2d / nn.Conv1d (zero padding ph/pw, stride sh/sw, no dilation/groups) as implicit GEMM
+ * nn.Conv2d / nn.Conv1d (zero padding ph/pw, stride sh/sw, no groups; dilation: srk_conv1d_nlc_dil_*) as implicit GEMM
  * on CHANNELS-LAST activations: x [N][H][W][Ci], y [N][Ho][Wo][Co], Ho = (H + 2ph - KH)/sh + 1.
  * Weights stay in torch layout w [Co][Ci][KH][KW] (the state_dict tensor), bias [Co] (nullable).
  * ws: srk_conv2d_workspace_floats() floats (re-laid-out weights).  The 1-D convolutions of
@@ -316,6 +316,21 @@ int srk_conv2d_nhwc_bwd16_acc(const float* x, int64_t N, int64_t H, int64_t W, i
                               int64_t Co, int64_t KH, int64_t KW, int64_t ph, int64_t pw, int64_t sh, int64_t sw,
                               const float* dy, const void* dy16, float* dx, float* dw, float* db, float* ws,
                               const void* x16, int dw_accumulate, void* stream);
+/* Dilated nn.Conv1d (stride 1, zero padding pad, dilation dil >= 1; model_resnet_dconv.py:98-100) on
+ * CHANNELS-LAST activations: x [N][L][Ci], w [Co][Ci][K] (torch layout), bias [Co] (nullable),
+ * y [N][Lo][Co] with Lo = L + 2 pad - dil (K - 1).  The same implicit GEMMs as above (H = 1, KH = 1) with
+ * tap k gathered k * dil columns from tap 0, in fp32 and with bf16 / fp16 operands.
+ * ws: srk_conv2d_workspace_floats(Ci, Co, 1, K) floats.  x16 / x16_written, dy16 and dw_accumulate mean
+ * what they mean on srk_conv2d_nhwc_fwd16 / _bwd16_acc (all nullable / 0).  dil = 1 forwards to those entry
+ * points (bitwise their results).  Backward writes dw [Co][Ci][K], db (nullable) and dx (nullable).
+ * Checked on the host before any device work, SRK_ERR_INVALID with "dilation" in srk_last_error():
+ * dil < 1, Lo < 1, a null x, w, y (fwd) / dy, dw (bwd) or ws.                                   */
+int srk_conv1d_nlc_dil_fwd(const float* x, int64_t N, int64_t L, int64_t Ci, const float* w, const float* bias,
+                           int64_t Co, int64_t K, int64_t pad, int64_t dil, float* y, float* ws,
+                           void* x16, int* x16_written, void* stream);
+int srk_conv1d_nlc_dil_bwd(const float* x, int64_t N, int64_t L, int64_t Ci, const float* w, int64_t Co, int64_t K,
+                           int64_t pad, int64_t dil, const float* dy, const void* dy16, float* dx, float* dw,
+                           float* db, float* ws, const void* x16, int dw_accumulate, void* stream);
 /* Conv2d (stride 1) + bias + MaxPool2d((1, 4)) fused (model_fbanks_cnn.py:74-75,91-92: conv2 then
  * maxpool2): the implicit GEMM's epilogue pools its own output, so only the pooled activation y
  * [N][Ho][Wo/4][Co] and the uint8 window argmax [N][Ho][Wo/4][Co] (first maximum, NaN wins: the

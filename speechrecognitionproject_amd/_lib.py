@@ -81,6 +81,8 @@ _SIGS = {
                                    _P, _P, _P, _P, _P, _P],
     "srk_conv2d_nhwc_bwd16_acc": [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P,
                                   _P, _P, _P, _P, _P, _I, _P],
+    "srk_conv1d_nlc_dil_fwd": [_P, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, ctypes.POINTER(_I), _P],
+    "srk_conv1d_nlc_dil_bwd": [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _I, _P],
     "srk_conv2d_nhwc_fwd_pool": [_P, _I64, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P,
                                  _P, ctypes.POINTER(_I), _P],
     "srk_conv2d_nhwc_bwd_pool": [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P,

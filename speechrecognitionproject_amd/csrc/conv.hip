@@ -39,6 +39,9 @@ struct FastDiv {
 
 struct ConvArgs {
   int N, H, W, Ci, Ho, Wo, Co, KH, KW, ph, pw, sh, sw;
+  // dilation along the width (srk_conv1d_nlc_dil_*): tap kw sits kw * dil columns from tap 0.  1 on every other
+  // entry point; > 1 only with stride 1, and never on the pooled (UNPOOL / pool_w) or row-staged paths
+  int dil = 1;
   const float* x;      // [N][H][W][Ci]
   const float* dy;     // [N][Ho][Wo][Co]
   const float* wmat;   // fwd: Wt [KH*KW*Ci][Co]; dgrad: Wd [KH*KW*Co][Ci]
@@ -78,9 +81,9 @@ struct ConvArgs {
 // the position is outside the image / problem) and whether it is valid; the caller loads
 // unconditionally and zeroes invalid values at LDS-store time (after the stage's MFMAs), so no load
 // is exec-masked and no select waits on a load in front of the MFMAs.
-//   fwd   A[m = pixel (n,ho,wo)][k = (kh,kw,ci)] = X[n, ho*sh+kh-ph, wo*sw+kw-pw, ci]
-//   dgrad A[m = pixel (n,h,w)][k = (kh,kw,co)]   = dY[n, (h+ph-kh)/sh, (w+pw-kw)/sw, co] (exact division only)
-//   wgrad A[m = (kh,kw,ci)][k = pixel (n,ho,wo)] = X[n, ho*sh+kh-ph, wo*sw+kw-pw, ci]
+//   fwd   A[m = pixel (n,ho,wo)][k = (kh,kw,ci)] = X[n, ho*sh+kh-ph, wo*sw+kw*dil-pw, ci]
+//   dgrad A[m = pixel (n,h,w)][k = (kh,kw,co)]   = dY[n, (h+ph-kh)/sh, (w+pw-kw*dil)/sw, co] (exact division only)
+//   wgrad A[m = (kh,kw,ci)][k = pixel (n,ho,wo)] = X[n, ho*sh+kh-ph, wo*sw+kw*dil-pw, ci]
 struct Pix { int n, a, b; bool ok; };   // pixel (n, row, col) + "row index < rows"
 
 __device__ __forceinline__ Pix split_pix(int64_t p, int64_t rows, const FastDiv& fw, const FastDiv& fh) {
@@ -106,12 +109,12 @@ __device__ __forceinline__ Tap split_tap(int64_t k, const FastDiv& fc, const Fas
 template <int MODE>
 __device__ __forceinline__ int64_t a_offset(const ConvArgs& c, const Pix& p, const Tap& t, bool& ok) {
   if (MODE == kDgrad) {
-    const int ht = p.a + c.ph - t.kh, wt = p.b + c.pw - t.kw;
+    const int ht = p.a + c.ph - t.kh, wt = p.b + c.pw - t.kw * c.dil;
     const int ho = (int)c.fd_sh.div(ht > 0 ? (unsigned)ht : 0u), wo = (int)c.fd_sw.div(wt > 0 ? (unsigned)wt : 0u);
     ok = ok && p.ok && ht >= 0 && wt >= 0 && ho * c.sh == ht && wo * c.sw == wt && ho < c.Ho && wo < c.Wo;
     return ok ? (((int64_t)p.n * c.Ho + ho) * c.Wo + wo) * c.Co + t.ch : 0;
   }
-  const int hi = p.a * c.sh + t.kh - c.ph, wi = p.b * c.sw + t.kw - c.pw;
+  const int hi = p.a * c.sh + t.kh - c.ph, wi = p.b * c.sw + t.kw * c.dil - c.pw;
   ok = ok && p.ok && hi >= 0 && hi < c.H && wi >= 0 && wi < c.W;
   return ok ? (((int64_t)p.n * c.H + hi) * c.W + wi) * c.Ci + t.ch : 0;
 }
@@ -268,7 +271,8 @@ __global__ __launch_bounds__(NW * 64) void conv_gemm_kernel(ConvArgs c) {
           const int chans = MODE == kDgrad ? c.Co : c.Ci;
           const int tap = __builtin_amdgcn_readfirstlane((int)((unsigned)k0 / (unsigned)chans));
           const int ch = (int)k0 - tap * chans + aq;
-          const int kh = __builtin_amdgcn_readfirstlane(tap / c.KW), kw = tap - kh * c.KW;
+          const int kh = __builtin_amdgcn_readfirstlane(tap / c.KW);
+          const int kw = (tap - kh * c.KW) * c.dil;   // the tap's column shift
           const bool kin = k0 + aq < ke;
 #pragma unroll
           for (int i = 0; i < VA; ++i) {
@@ -1099,8 +1103,8 @@ void launch_conv(const ConvArgs& c, dim3 grid, hipStream_t s, bool vec, bool vec
 // multiple of 16, a K-tile lies inside one tap (kh, kw), so per K-tile each lane recomputes its unit's
 // source offset from its pixel (decomposed once per tile) and the uniform tap; a unit outside the
 // image, past the problem or past the split's k end is read past num_records, i.e. as zeros.
-//   fwd   A = X[n, a + kh - ph, b + kw - pw, ch..ch+3]       (KC: 4 channels of one pixel per unit)
-//   dgrad A = dY[n, a + ph - kh, b + pw - kw, ch..ch+3]      (KC, stride 1)
+//   fwd   A = X[n, a + kh - ph, b + kw dil - pw, ch..ch+3]   (KC: 4 channels of one pixel per unit)
+//   dgrad A = dY[n, a + ph - kh, b + pw - kw dil, ch..ch+3]  (KC, stride 1)
 //   wgrad A^T unit = X[pixel k (+ tap), ci..ci+3]           (TR: 4 channels at one pixel per unit)
 //   B = the re-laid-out weights [K][N] (fwd / dgrad) or dY [pixels][Co] (wgrad): plain row-major
 // Epilogue straight from the accumulators (the 96-KB ring of BN = 128 leaves no room to stage),
@@ -1191,7 +1195,8 @@ __global__ __launch_bounds__(512, 1) void conv_ring_kernel(ConvArgs c) {
     // fwd / dgrad: the K-tile's tap and channel base (uniform: chans % 16 == 0, k0 % 16 == 0)
     const unsigned tap = AKC ? (unsigned)__builtin_amdgcn_readfirstlane(c.fd_c.div((unsigned)k0)) : 0u;
     const int ch0 = (int)((unsigned)k0 - tap * (unsigned)chans);
-    const int kh = (int)c.fd_kw.div(tap), kw = (int)(tap - (unsigned)kh * c.KW);
+    const int kh = (int)c.fd_kw.div(tap);
+    const int kw = (int)(tap - (unsigned)kh * c.KW) * c.dil;   // the tap's column shift
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       unsigned v = kROOB;
@@ -1213,7 +1218,7 @@ __global__ __launch_bounds__(512, 1) void conv_ring_kernel(ConvArgs c) {
         const int64_t k = k0 + akk[h];    // the unit's pixel (output grid)
         const Pix q = split_pix(k < ke ? k : 0, c.K, c.fd_w, c.fd_h);
         const Tap& t4 = atap[h];
-        const int hi = q.a * c.sh + t4.kh - c.ph, wi = q.b * c.sw + t4.kw - c.pw;
+        const int hi = q.a * c.sh + t4.kh - c.ph, wi = q.b * c.sw + t4.kw * c.dil - c.pw;
         const bool ok = aok[h] && k < ke && hi >= 0 && hi < c.H && wi >= 0 && wi < c.W;
         if (ok) v = (unsigned)(((((int64_t)q.n * c.H + hi) * c.W + wi) * c.Ci + t4.ch) * 4);
       }
@@ -1497,7 +1502,8 @@ __global__ __launch_bounds__(512, 1) void conv_ring16_kernel(ConvArgs c) {
     const unsigned ldst = lds0 + (unsigned)((g % NST) * STAGE * 2);
     const unsigned tap = AKC ? (unsigned)__builtin_amdgcn_readfirstlane(c.fd_c.div((unsigned)k0)) : 0u;
     const int ch0 = (int)((unsigned)k0 - tap * (unsigned)chans);
-    const int kh = (int)c.fd_kw.div(tap), kw = (int)(tap - (unsigned)kh * c.KW);
+    const int kh = (int)c.fd_kw.div(tap);
+    const int kw = (int)(tap - (unsigned)kh * c.KW) * c.dil;   // the tap's column shift
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       unsigned v = kROOB;
@@ -1519,7 +1525,7 @@ __global__ __launch_bounds__(512, 1) void conv_ring16_kernel(ConvArgs c) {
         const int64_t k = k0 + akk[h];
         const Pix q = split_pix(k < T.ke ? k : 0, c.K, c.fd_w, c.fd_h);
         const Tap& t4 = T.atap[h];
-        const int hi = q.a * c.sh + t4.kh - c.ph, wi = q.b * c.sw + t4.kw - c.pw;
+        const int hi = q.a * c.sh + t4.kh - c.ph, wi = q.b * c.sw + t4.kw * c.dil - c.pw;
         const bool ok = T.aok[h] && k < T.ke && hi >= 0 && hi < c.H && wi >= 0 && wi < c.W;
         if (ok) v = (unsigned)(((((int64_t)q.n * c.H + hi) * c.W + wi) * c.Ci + t4.ch) * 2);
       }
@@ -2951,11 +2957,11 @@ int conv2_bwd16_pooled(const float* x, int64_t N, int64_t H, const float* w, con
 }
 
 int check(int64_t N, int64_t H, int64_t W, int64_t Ci, int64_t Co, int64_t KH, int64_t KW, int64_t ph, int64_t pw,
-          int64_t sh, int64_t sw, int64_t* Ho, int64_t* Wo) {
+          int64_t sh, int64_t sw, int64_t* Ho, int64_t* Wo, int64_t dil = 1) {
   SRK_REQUIRE(N > 0 && H > 0 && W > 0 && Ci > 0 && Co > 0 && KH > 0 && KW > 0 && ph >= 0 && pw >= 0 && sh > 0 && sw > 0,
               SRK_ERR_INVALID, "conv: bad dims");
   *Ho = (H + 2 * ph - KH) / sh + 1;
-  *Wo = (W + 2 * pw - KW) / sw + 1;
+  *Wo = (W + 2 * pw - dil * (KW - 1) - 1) / sw + 1;
   SRK_REQUIRE(*Ho > 0 && *Wo > 0, SRK_ERR_INVALID, "conv: empty output");
   SRK_REQUIRE(N * H * W * Ci < ((int64_t)1 << 40) && N * (*Ho) * (*Wo) * Co < ((int64_t)1 << 40), SRK_ERR_INVALID,
               "conv: too large");
@@ -2975,14 +2981,17 @@ int srk_conv2d_nhwc_fwd(const float* x, int64_t N, int64_t H, int64_t W, int64_t
   return srk_conv2d_nhwc_fwd16(x, N, H, W, Ci, w, bias, Co, KH, KW, ph, pw, sh, sw, y, ws, nullptr, nullptr, stream);
 }
 
-int srk_conv2d_nhwc_fwd16(const float* x, int64_t N, int64_t H, int64_t W, int64_t Ci, const float* w,
-                          const float* bias, int64_t Co, int64_t KH, int64_t KW, int64_t ph, int64_t pw, int64_t sh,
-                          int64_t sw, float* y, float* ws, void* x16, int* x16_written, void* stream) {
-  SRK_API_BEGIN
+}  // extern "C"
+
+namespace srk {
+// the conv forward; dil > 1 (srk_conv1d_nlc_dil_fwd: KH = 1, stride 1) only reaches the implicit GEMMs
+int conv_fwd(const float* x, int64_t N, int64_t H, int64_t W, int64_t Ci, const float* w, const float* bias,
+             int64_t Co, int64_t KH, int64_t KW, int64_t ph, int64_t pw, int64_t sh, int64_t sw, int64_t dil, float* y,
+             float* ws, void* x16, int* x16_written, void* stream) {
   const bool x16_ready = x16 && x16_written && *x16_written == 2;   // the producer's copy (srk_batchnorm_fwd16)
   if (x16_written) *x16_written = 0;
   int64_t Ho, Wo;
-  if (int rc = srk::check(N, H, W, Ci, Co, KH, KW, ph, pw, sh, sw, &Ho, &Wo)) return rc;
+  if (int rc = srk::check(N, H, W, Ci, Co, KH, KW, ph, pw, sh, sw, &Ho, &Wo, dil)) return rc;
   SRK_REQUIRE(x && w && y && ws, SRK_ERR_INVALID, "conv fwd: null pointer");
   hipStream_t s = srk::as_stream(stream);
   const int64_t nw = Co * Ci * KH * KW;
@@ -2991,12 +3000,14 @@ int srk_conv2d_nhwc_fwd16(const float* x, int64_t N, int64_t H, int64_t W, int64
   srk::ConvArgs c{};
   c.N = (int)N; c.H = (int)H; c.W = (int)W; c.Ci = (int)Ci; c.Ho = (int)Ho; c.Wo = (int)Wo; c.Co = (int)Co;
   c.KH = (int)KH; c.KW = (int)KW; c.ph = (int)ph; c.pw = (int)pw; c.sh = (int)sh; c.sw = (int)sw;
+  c.dil = (int)dil;
   c.x = x; c.wmat = ws; c.out = y; c.bias = bias;
   c.M = N * Ho * Wo; c.Nn = Co; c.K = KH * KW * Ci;
   // A full-width "valid" conv (model_fbanks_cnn.py:74, conv3 (1, 10) on width 10) is the plain GEMM
   //   Y[(n,h)][co] = X[(n,h)][(kw,ci)] . Wt[(kw,ci)][co] + bias
   // (x rows are already the GEMM rows: no gather, no split-K slabs of the implicit GEMM's tall 2-tile-wide grid)
-  const bool full_width = KH == 1 && ph == 0 && pw == 0 && sh == 1 && KW == W && Wo == 1 && srk::g_opt_conv_fw_gemm;
+  const bool full_width =
+      KH == 1 && ph == 0 && pw == 0 && sh == 1 && KW == W && Wo == 1 && dil == 1 && srk::g_opt_conv_fw_gemm;
   auto fw_gemm = [&](const unsigned short* a16, const unsigned short* b16, const char* cat) -> int {
     srk::GemmDesc g;
     g.M = N * H; g.N = Co; g.K = KW * Ci;
@@ -3031,6 +3042,16 @@ int srk_conv2d_nhwc_fwd16(const float* x, int64_t N, int64_t H, int64_t W, int64
   }
   if (full_width) return fw_gemm(c.a16, c.b16, prec == srk::kPrecF32 ? "conv_fwd" : "conv_fwd_lp");
   return srk::run_conv_gemm<srk::kFwd>(c, s, "conv_fwd");
+}
+}  // namespace srk
+
+extern "C" {
+
+int srk_conv2d_nhwc_fwd16(const float* x, int64_t N, int64_t H, int64_t W, int64_t Ci, const float* w,
+                          const float* bias, int64_t Co, int64_t KH, int64_t KW, int64_t ph, int64_t pw, int64_t sh,
+                          int64_t sw, float* y, float* ws, void* x16, int* x16_written, void* stream) {
+  SRK_API_BEGIN
+  return srk::conv_fwd(x, N, H, W, Ci, w, bias, Co, KH, KW, ph, pw, sh, sw, 1, y, ws, x16, x16_written, stream);
   SRK_API_END
 }
 
@@ -3048,19 +3069,24 @@ namespace srk {
 int conv_bwd(const float* x, int64_t N, int64_t H, int64_t W, int64_t Ci, const float* w, int64_t Co, int64_t KH,
              int64_t KW, int64_t ph, int64_t pw, int64_t sh, int64_t sw, const float* dy, const uint8_t* dy_arg,
              float* dx, float* dw, float* db, float* ws, const void* x16, void* stream,
-             const unsigned short* dy16 = nullptr, int dw_accumulate = 0) {
+             const unsigned short* dy16 = nullptr, int dw_accumulate = 0, int64_t dil = 1) {
   int64_t Ho, Wo;
-  if (int rc = srk::check(N, H, W, Ci, Co, KH, KW, ph, pw, sh, sw, &Ho, &Wo)) return rc;
+  if (int rc = srk::check(N, H, W, Ci, Co, KH, KW, ph, pw, sh, sw, &Ho, &Wo, dil)) return rc;
+  // dilation (srk_conv1d_nlc_dil_bwd): the implicit GEMMs only — never the pooled gradient, and the
+  // row-staged / full-width branches below are skipped
+  SRK_REQUIRE(dil == 1 || (!dy_arg && sh == 1 && sw == 1), SRK_ERR_INTERNAL,
+              "conv bwd: dilation needs stride 1 and a dense dY");
   SRK_REQUIRE(x && w && (dy || dy16) && dw && ws, SRK_ERR_INVALID, "conv bwd: null pointer");
   hipStream_t s = srk::as_stream(stream);
   const int64_t nw = Co * Ci * KH * KW;
   srk::ConvArgs c{};
   c.N = (int)N; c.H = (int)H; c.W = (int)W; c.Ci = (int)Ci; c.Ho = (int)Ho; c.Wo = (int)Wo; c.Co = (int)Co;
   c.KH = (int)KH; c.KW = (int)KW; c.ph = (int)ph; c.pw = (int)pw; c.sh = (int)sh; c.sw = (int)sw;
+  c.dil = (int)dil;
   c.x = x; c.dy = dy;
   c.dy_arg = dy_arg;
   int rc;
-  const bool full_width = KH == 1 && ph == 0 && sh == 1 && pw == 0 && KW == W && Wo == 1;
+  const bool full_width = KH == 1 && ph == 0 && sh == 1 && pw == 0 && KW == W && Wo == 1 && dil == 1;
   SRK_REQUIRE(!dy_arg || (!full_width && (!db || srk::g_opt_conv_fused_db)), SRK_ERR_INTERNAL,
               "conv bwd: pooled dY needs the implicit data gradient and the fused bias sums");
   // dy16 without dy: the caller's 16-bit dY only (the pooled backward): the implicit 16-bit-source GEMMs, no
@@ -3111,8 +3137,8 @@ int conv_bwd(const float* x, int64_t N, int64_t H, int64_t W, int64_t Ci, const 
     prof.detail("conv_dgrad_as_gemm %lldx%lldx%lld", (long long)g.M, (long long)g.N, (long long)g.K);
     prof.bytes(4.0 * ((double)g.M * g.K + (double)g.K * g.N + (double)g.M * g.N));
     if ((rc = srk::gemm_f32(g, s))) return rc;
-  } else if (dgrad_implicit && d16[0] && srk::g_opt_conv_row16_dgrad && KH == 1 && KW == 7 && ph == 0 && pw == 3 &&
-             sh == 1 && sw == 1 && W == 40 && Ci == 64 && Co == 128 && (N * H) < (1LL << 30) / (W * Co)) {
+  } else if (dgrad_implicit && d16[0] && dil == 1 && srk::g_opt_conv_row16_dgrad && KH == 1 && KW == 7 && ph == 0 &&
+             pw == 3 && sh == 1 && sw == 1 && W == 40 && Ci == 64 && Co == 128 && (N * H) < (1LL << 30) / (W * Co)) {
     // fbanks_cnn conv2's data gradient: the row-staged kernel (conv_row16_dgrad_kernel)
     srk::RowDgArgs ra{};
     ra.dy16 = d16[1];
@@ -3239,6 +3265,44 @@ int srk_conv2d_nhwc_bwd16_acc(const float* x, int64_t N, int64_t H, int64_t W, i
   SRK_REQUIRE(dy, SRK_ERR_INVALID, "conv bwd: null pointer");
   return srk::conv_bwd(x, N, H, W, Ci, w, Co, KH, KW, ph, pw, sh, sw, dy, nullptr, dx, dw, db, ws, x16, stream,
                        static_cast<const unsigned short*>(dy16), dw_accumulate ? 1 : 0);
+  SRK_API_END
+}
+
+// Dilated nn.Conv1d (stride 1) on channels-last [N][L][Ci]: the H = 1, KH = 1 implicit GEMMs with tap k gathered
+// k * dil columns from tap 0 (ConvArgs::dil).  Arguments are checked on the host before any device work.
+int srk_conv1d_nlc_dil_fwd(const float* x, int64_t N, int64_t L, int64_t Ci, const float* w, const float* bias,
+                           int64_t Co, int64_t K, int64_t pad, int64_t dil, float* y, float* ws, void* x16,
+                           int* x16_written, void* stream) {
+  SRK_API_BEGIN
+  SRK_REQUIRE(dil >= 1, SRK_ERR_INVALID, "conv1d dilation: dil = %lld, must be >= 1", (long long)dil);
+  SRK_REQUIRE(N > 0 && L > 0 && Ci > 0 && Co > 0 && K > 0 && pad >= 0 && pad < (1 << 28) && dil < (1 << 20) && K < (1 << 20),
+              SRK_ERR_INVALID, "conv1d dilation: bad dims");
+  SRK_REQUIRE(L + 2 * pad - dil * (K - 1) >= 1, SRK_ERR_INVALID,
+              "conv1d dilation: empty output (L %lld + 2 pad %lld < receptive field %lld)", (long long)L, (long long)pad,
+              (long long)(dil * (K - 1) + 1));
+  SRK_REQUIRE(x && w && y && ws, SRK_ERR_INVALID, "conv1d dilation fwd: null pointer");
+  if (dil == 1)
+    return srk_conv2d_nhwc_fwd16(x, N, 1, L, Ci, w, bias, Co, 1, K, 0, pad, 1, 1, y, ws, x16, x16_written, stream);
+  return srk::conv_fwd(x, N, 1, L, Ci, w, bias, Co, 1, K, 0, pad, 1, 1, dil, y, ws, x16, x16_written, stream);
+  SRK_API_END
+}
+
+int srk_conv1d_nlc_dil_bwd(const float* x, int64_t N, int64_t L, int64_t Ci, const float* w, int64_t Co, int64_t K,
+                           int64_t pad, int64_t dil, const float* dy, const void* dy16, float* dx, float* dw,
+                           float* db, float* ws, const void* x16, int dw_accumulate, void* stream) {
+  SRK_API_BEGIN
+  SRK_REQUIRE(dil >= 1, SRK_ERR_INVALID, "conv1d dilation: dil = %lld, must be >= 1", (long long)dil);
+  SRK_REQUIRE(N > 0 && L > 0 && Ci > 0 && Co > 0 && K > 0 && pad >= 0 && pad < (1 << 28) && dil < (1 << 20) && K < (1 << 20),
+              SRK_ERR_INVALID, "conv1d dilation: bad dims");
+  SRK_REQUIRE(L + 2 * pad - dil * (K - 1) >= 1, SRK_ERR_INVALID,
+              "conv1d dilation: empty output (L %lld + 2 pad %lld < receptive field %lld)", (long long)L, (long long)pad,
+              (long long)(dil * (K - 1) + 1));
+  SRK_REQUIRE(x && w && dy && dw && ws, SRK_ERR_INVALID, "conv1d dilation bwd: null pointer");
+  if (dil == 1)
+    return srk_conv2d_nhwc_bwd16_acc(x, N, 1, L, Ci, w, Co, 1, K, 0, pad, 1, 1, dy, dy16, dx, dw, db, ws, x16,
+                                     dw_accumulate, stream);
+  return srk::conv_bwd(x, N, 1, L, Ci, w, Co, 1, K, 0, pad, 1, 1, dy, nullptr, dx, dw, db, ws, x16, stream,
+                       static_cast<const unsigned short*>(dy16), dw_accumulate ? 1 : 0, dil);
   SRK_API_END
 }
 

@@ -442,25 +442,94 @@ class Conv2d(tnn.Module):
         return _Conv2dNHWCFn.apply(x, self.weight, self.bias, self.padding, self.stride)
 
 
+class _Conv1dDilFn(torch.autograd.Function):
+    """Dilated 1-D convolution (stride 1) on channels-last [N, L, Ci] through srk_conv1d_nlc_dil_fwd / _bwd: the
+    arguments, 16-bit copies and in-place weight gradient of _Conv2dNHWCFn, plus the dilation."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, padding, dilation):
+        x = x.contiguous()
+        w_param = w
+        w = w.contiguous()
+        _check_cuda(x, w, b)
+        N, L, Ci = x.shape
+        Co, Ci2, K = w.shape
+        if Ci2 != Ci:
+            raise _lib.SrkError("conv: input has %d channels, weight expects %d" % (Ci, Ci2))
+        Lo = L + 2 * padding - dilation * (K - 1)
+        y = torch.empty((N, max(Lo, 0), Co), device=x.device)
+        ws = torch.empty(int(_lib.lib().srk_conv2d_workspace_floats(Ci, Co, 1, K)), device=x.device)
+        x16, written = None, ctypes.c_int(0)
+        if _lib.matmul_precision() != "fp32" and Ci % 8 == 0 and Co % 8 == 0:
+            x16 = _copy16_get(x)   # the producing BatchNorm's copy (written = 2: ready)
+            if x16 is not None:
+                written.value = 2
+            elif ctx.needs_input_grad[1]:
+                x16 = torch.empty(x.numel(), device=x.device, dtype=torch.int16)
+        call("srk_conv1d_nlc_dil_fwd", ptr(x), N, L, Ci, ptr(w), ptr(b) if b is not None else None, Co, K, padding,
+             dilation, ptr(y), ptr(ws), ptr(x16) if x16 is not None else None, ctypes.byref(written), stream_ptr())
+        ctx.x16 = x16 if written.value else None
+        ctx.prec = _lib.matmul_precision()
+        ctx.save_for_backward(x, w)
+        ctx.w_param = w_param
+        ctx.geom = (padding, dilation, b is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        pad, dil, has_b = ctx.geom
+        N, L, Ci = x.shape
+        Co, _, K = w.shape
+        dy = dy.contiguous()
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        # the weight gradient ADDED to a FlatParams-owned .grad in the layout kernel (no autograd add kernel)
+        gw = _flat_grad(ctx.w_param) if ctx.needs_input_grad[1] and INPLACE_GRADS else None
+        dw = gw if gw is not None else torch.empty_like(w)
+        db = torch.empty((Co,), device=x.device) if has_b else None
+        ws = torch.empty(int(_lib.lib().srk_conv2d_workspace_floats(Ci, Co, 1, K)), device=x.device)
+        x16 = ctx.x16 if ctx.prec == _lib.matmul_precision() else None   # a copy in this precision only
+        ctx.x16 = None
+        dy16 = _copy16_get(dy, pop=True)   # the producing BatchNorm backward's copy of dY
+        call("srk_conv1d_nlc_dil_bwd", ptr(x), N, L, Ci, ptr(w), Co, K, pad, dil, ptr(dy),
+             ptr(dy16) if dy16 is not None else None, ptr(dx) if dx is not None else None, ptr(dw),
+             ptr(db) if db is not None else None, ptr(ws), ptr(x16) if x16 is not None else None,
+             1 if gw is not None else 0, stream_ptr())
+        if gw is not None:
+            red = _reducer_of(ctx.w_param)
+            if red is not None:
+                red.mark_ready([ctx.w_param])
+            dw = None
+        else:
+            dw = dw.view(ctx.w_param.shape)
+        return dx, dw, db, None, None
+
+
 class Conv1d(tnn.Module):
     """nn.Conv1d-compatible parameters (weight [Co, Ci, K]) on channels-last input [N, L, Ci]."""
 
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True):
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True, dilation=1):
         super().__init__()
-        ref = tnn.Conv1d(in_channels, out_channels, kernel_size, stride=stride, padding=padding, bias=bias)
+        ref = tnn.Conv1d(in_channels, out_channels, kernel_size, stride=stride, padding=padding, bias=bias,
+                         dilation=dilation)
         self.in_channels, self.out_channels = in_channels, out_channels
-        self.kernel_size, self.stride, self.padding = ref.kernel_size, ref.stride, ref.padding
+        self.kernel_size, self.stride, self.padding, self.dilation = ref.kernel_size, ref.stride, ref.padding, ref.dilation
         self.weight = tnn.Parameter(ref.weight.detach().clone())
         self.bias = tnn.Parameter(ref.bias.detach().clone()) if bias else None
 
     def forward(self, x):
-        return conv1d_nlc(x, self.weight, self.bias, self.stride[0], self.padding[0])
+        return conv1d_nlc(x, self.weight, self.bias, self.stride[0], self.padding[0], self.dilation[0])
 
 
-def conv1d_nlc(x, weight, bias=None, stride=1, padding=0):
-    """K6 1-D convolution of channels-last [N, L, Ci] input with an nn.Conv1d weight [Co, Ci, K]."""
+def conv1d_nlc(x, weight, bias=None, stride=1, padding=0, dilation=1):
+    """K6 1-D convolution of channels-last [N, L, Ci] input with an nn.Conv1d weight [Co, Ci, K]; dilation > 1
+    (stride 1 only) runs the dilated gathers of srk_conv1d_nlc_dil_*."""
     require_gpu()
     N, L, C = x.shape
+    if dilation != 1:
+        if stride != 1:
+            raise _lib.SrkError("conv1d: dilation %d needs stride 1, got %d" % (dilation, stride))
+        return _Conv1dDilFn.apply(x, weight, bias, int(padding), int(dilation))
     y = _Conv2dNHWCFn.apply(x.reshape(N, 1, L, C), weight, bias, (0, padding), (1, stride))
     return y.reshape(N, y.shape[2], weight.shape[0])
 
