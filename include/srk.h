@@ -488,6 +488,28 @@ int srk_uniform_f64_state(uint64_t* state, double lo, double hi, int64_t n, doub
 /* y = keep ? x * scale : 0 (dropout with an explicit keep-mask; also its backward).          */
 int srk_dropout_apply(const float* x, const uint8_t* keep, int64_t n, float scale, float* y, void* stream);
 
+/* ---------------------------------------------------------------- attention pooling over time
+ * A query scores every step of a sequence, a softmax over time weights them, the weighted sum is the
+ * context (nn.AttentionPool over a BiGRU's output; no reference counterpart):
+ *   s[b,t] = scale * <q[b,:], y[b,t,:]>, alpha[b,:] = softmax_t(s[b,:]) (max-subtracted),
+ *   ctx[b,:] = sum_t alpha[b,t] * y[b,t,:].
+ * y [B][T][D] contiguous, q / ctx / dctx / dq [B][D], alpha [B][T]; fp32 at every matmul precision.
+ * Backward, g = dctx: a_t = <g, y_t>, m = sum_t alpha_t a_t, ds_t = alpha_t (a_t - m),
+ *   dq = scale * sum_t ds_t y_t, dy_t = alpha_t g + scale * ds_t q   (dy fully written, not accumulated;
+ *   alpha is an output only: no gradient flows into it).
+ * One workgroup per clip, one launch per call; every reduction has a fixed order and there are no
+ * floating-point atomics, so equal inputs give equal bits (eagerly and from a replayed graph).
+ * T <= 64 and D <= 1024 with D % 4 == 0 and 16-byte aligned tensors keep the clip in registers (y is read
+ * once); other shapes take two passes over y, the second one out of the caches, with scalar accesses when
+ * D % 4 != 0 (srk_set_option "attn_pool_regs", default 1; 0 = always two passes: A/B measurements and tests).
+ * Checked on the host before any device work, SRK_ERR_INVALID with "attn_pool" in srk_last_error():
+ * B < 1, T outside 1..1024, D outside 1..4096, a scale that is not finite, any null tensor.
+ * Profiler category "attn_pool" (one record per launch, with its algorithmic bytes).            */
+int srk_attn_pool_fwd(const float* y, const float* q, int64_t B, int64_t T, int64_t D, float scale, float* ctx,
+                      float* alpha, void* stream);
+int srk_attn_pool_bwd(const float* y, const float* q, const float* alpha, const float* dctx, int64_t B, int64_t T,
+                      int64_t D, float scale, float* dy, float* dq, void* stream);
+
 /* ---------------------------------------------------------------- diagnostics (tests only)
  * Directed checks of two instruction patterns (csrc/diag.hip; tests/test_diag_gpu.py):
  * srk_diag_acc_store: the row-staged data gradient's epilogue (raw buffer stores of 32x32 MFMA

@@ -55,6 +55,7 @@ int g_opt_gru_dwhh_fused = 1;
 int g_opt_gru_fwd_worker = 0;
 int g_opt_gru_dwhh_batched = 1;
 int g_opt_gemm_skinny = 1;
+int g_opt_attn_pool_regs = 1;
 std::atomic<int64_t> g_scratch_gen{0};
 
 static thread_local std::string g_last_error;
@@ -515,6 +516,10 @@ int srk_set_option(const char* name, int64_t value) {
   }
   if (n == "gemm_skinny") {   // GEMMs with a dimension <= 16 on the VALU kernels (1) or the matrix-core tiles (0)
     srk::g_opt_gemm_skinny = value != 0;
+    return SRK_OK;
+  }
+  if (n == "attn_pool_regs") {   // attention pooling: register-resident clips where they fit (1) or two passes (0)
+    srk::g_opt_attn_pool_regs = value != 0;
     return SRK_OK;
   }
   if (n == "gru_dwhh_batched") {   // 16-bit GRU backward: both directions' dW_hh in one batched GEMM (1) or two (0)

@@ -168,6 +168,9 @@ extern int g_opt_mfcc_variant;
 // stream-K for fp32 ping-pong GEMMs whose 256 x 256 grid covers 1/2 .. 1 round of CUs ("gemm_streamk",
 // default 1)
 extern int g_opt_gemm_streamk;
+// attention pooling: clips that fit the register file are read once ("attn_pool_regs", default 1; 0 = every shape
+// on the two-pass kernel)
+extern int g_opt_attn_pool_regs;
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 

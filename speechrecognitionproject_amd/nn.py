@@ -195,6 +195,54 @@ def last_step(x):
     return _LastStepFn.apply(x)
 
 
+# ----------------------------------------------------------------------------- attention pooling
+class _AttentionPoolFn(torch.autograd.Function):
+    """srk_attn_pool_fwd / _bwd: alpha = softmax_t(scale <q, y_t>), ctx = sum_t alpha_t y_t.  fp32 at every
+    matmul precision (a softmax, like the loss); alpha is an output only."""
+
+    @staticmethod
+    def forward(ctx, y, q, scale):
+        y, q = y.contiguous(), q.contiguous()
+        _check_cuda(y, q)
+        if y.dim() != 3 or q.shape != (y.shape[0], y.shape[2]):
+            raise _lib.SrkError("attention pool: y must be [B, T, D] and q [B, D], got %s and %s"
+                                % (tuple(y.shape), tuple(q.shape)))
+        B, T, D = y.shape
+        out = torch.empty((B, D), device=y.device)
+        alpha = torch.empty((B, T), device=y.device)
+        call("srk_attn_pool_fwd", ptr(y), ptr(q), B, T, D, scale, ptr(out), ptr(alpha), stream_ptr())
+        ctx.save_for_backward(y, q, alpha)
+        ctx.scale = scale
+        ctx.mark_non_differentiable(alpha)
+        return out, alpha
+
+    @staticmethod
+    def backward(ctx, dctx, _dalpha):
+        y, q, alpha = ctx.saved_tensors
+        B, T, D = y.shape
+        dctx = dctx.contiguous()
+        dy, dq = torch.empty_like(y), torch.empty_like(q)
+        call("srk_attn_pool_bwd", ptr(y), ptr(q), ptr(alpha), ptr(dctx), B, T, D, ctx.scale, ptr(dy), ptr(dq),
+             stream_ptr())
+        return dy, dq, None
+
+
+class AttentionPool(tnn.Module):
+    """Attention pooling over time: ``forward(y [B, T, D], q [B, D]) -> (ctx [B, D], alpha [B, T])`` with
+    alpha = softmax over t of scale * <q, y_t> and ctx = sum_t alpha_t y_t, in one fused kernel each way.
+    ``scale`` defaults to 1 / sqrt(D).  No parameters; gradients flow to y and q, not into alpha (the per-step
+    weights are there to be looked at)."""
+
+    def __init__(self, scale=None):
+        super().__init__()
+        self.scale = scale
+
+    def forward(self, y, q):
+        require_gpu()
+        scale = float(self.scale) if self.scale is not None else y.shape[-1] ** -0.5
+        return _AttentionPoolFn.apply(y, q, scale)
+
+
 # ----------------------------------------------------------------------------- Linear
 class _LinearFn(torch.autograd.Function):
     @staticmethod

@@ -42,7 +42,8 @@ from ._lib import check_health
 from .nn import CrossEntropyLoss
 from .optim import Adam, FlatParams, LossScaler
 
-PLUGINS = ("mfcc_bgru", "fbanks_cnn", "spec_bgru", "resnet_bgru", "mfrn_bgru", "cnn_bgru", "spec_cnn", "resnet_dconv")
+PLUGINS = ("mfcc_bgru", "fbanks_cnn", "spec_bgru", "resnet_bgru", "mfrn_bgru", "cnn_bgru", "spec_cnn", "resnet_dconv",
+           "mfcc_bgru_att")
 
 
 def parse(argv=None):

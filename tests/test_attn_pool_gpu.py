@@ -1,0 +1,301 @@
+"""Attention pooling on the GPU: srk_attn_pool_fwd / _bwd against the float64 statement of
+tests/attn_pool_oracle.py, their determinism under eager runs and a replayed graph, nn.AttentionPool, and the
+mfcc_bgru_att plugin (model parity in float64, graphed train steps, 16-bit matmul precision).
+
+Bound of the kernel parity: max-norm relative error <= 1e-5 on ctx, alpha, dy and dq, the project's fp32 kernel
+bound (tests/test_dconv_gpu.py); torch's own float32 evaluation of the same formulas is within 9e-7 of float64 on
+these cases, so the bound leaves 10 x over plain float32 summation."""
+import functools
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+from attn_pool_oracle import MfccBGRUAtt, pool_case
+from oracle import models as OM
+from tolerances import LOGITS_REL, rel_err
+from speechrecognitionproject_amd import _lib
+from speechrecognitionproject_amd import nn as snn
+from speechrecognitionproject_amd.features import ptr, stream_ptr
+from speechrecognitionproject_amd.graphs import GraphedStep
+from speechrecognitionproject_amd.models import model_mfcc_bgru_att
+from speechrecognitionproject_amd.optim import Adam, FlatParams
+from speechrecognitionproject_amd.synthetic import synthetic_clips
+
+pytestmark = pytest.mark.gpu
+
+CASES = [  # B, T, D, scale, q multiplier
+    (3, 51, 1024, 1 / 32, 1),          # the model shape
+    (3, 51, 1024, 1.0, 1),             # peaky: the largest weight is about 1
+    (2, 1, 64, 0.125, 1),              # T = 1: alpha == 1 and dq == 0 exactly
+    (5, 7, 192, 192 ** -0.5, 1),
+    (2, 98, 130, 1.0, 0.2),            # D misses the vector width
+    (4, 49, 320, 320 ** -0.5, 3),
+    (2, 128, 2048, 2048 ** -0.5, 1),   # beyond the register-resident budget
+    (300, 51, 256, 1 / 16, 1),         # more clips than CUs
+]
+OVERFLOW = (2, 51, 1024, 1.0, 40)      # scores of several hundred
+
+
+def _in_registers(case):
+    return case[1] <= 64 and case[2] <= 1024 and case[2] % 4 == 0
+
+
+@functools.lru_cache(maxsize=None)
+def _case(case):
+    """The float64 inputs and results of a case, computed once and shared (never written to)."""
+    return pool_case(*case)
+
+
+def _raw(case, y, q, dctx, alpha_in=None):
+    """The two entry points on device tensors: (ctx, alpha, dy, dq)."""
+    B, T, D, scale, _ = case
+    ctx, alpha = torch.empty((B, D), device="cuda"), torch.empty((B, T), device="cuda")
+    dy, dq = torch.empty_like(y), torch.empty_like(q)
+    _lib.call("srk_attn_pool_fwd", ptr(y), ptr(q), B, T, D, scale, ptr(ctx), ptr(alpha), stream_ptr())
+    _lib.call("srk_attn_pool_bwd", ptr(y), ptr(q), ptr(alpha if alpha_in is None else alpha_in), ptr(dctx), B, T, D,
+              scale, ptr(dy), ptr(dq), stream_ptr())
+    return ctx, alpha, dy, dq
+
+
+def _device_inputs(case):
+    c = _case(case)
+    return tuple(c[k].float().cuda() for k in ("y", "q", "dctx"))
+
+
+def _check_parity(case, expect_kernel):
+    c = _case(case)
+    try:
+        _lib.prof_enable(1)
+        ctx, alpha, dy, dq = _raw(case, *_device_inputs(case))
+        torch.cuda.synchronize()
+        kernels = [k for k in _lib.prof_kernels() if k["name"] == "attn_pool"]
+        n, _, nbytes = _lib.prof_read("attn_pool")
+    finally:
+        _lib.prof_enable(0)
+    errs = {k: rel_err(v.cpu().numpy(), c[k].numpy()) for k, v in (("ctx", ctx), ("alpha", alpha), ("dy", dy))}
+    if case[1] == 1:   # the reference's dq is exactly 0: compared absolutely
+        errs["dq"] = float(dq.abs().max())
+        assert torch.equal(alpha, torch.ones_like(alpha))
+        assert errs["dq"] <= 1e-7, errs
+        errs["dq"] = 0.0
+    else:
+        errs["dq"] = rel_err(dq.cpu().numpy(), c["dq"].numpy())
+    print("attn_pool %s: %s" % (case, " ".join("%s %.2e" % kv for kv in errs.items())))
+    assert max(errs.values()) <= 1e-5, errs
+    # one launch each way, under the pool's own category, with its byte count
+    B, T, D = case[:3]
+    assert n == 2 and nbytes == 4.0 * (3 * B * T * D + 5 * B * D + 2 * B * T)
+    assert len(kernels) == 2 and all(expect_kernel in k["kernel"] and k["bytes"] > 0 for k in kernels), kernels
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_attn_pool_vs_float64(gpu, case):
+    _check_parity(case, "attn_pool_regs_kernel" if _in_registers(case) else "attn_pool_2pass_kernel")
+
+
+@pytest.mark.parametrize("case", [CASES[0], CASES[2], CASES[3], CASES[5]])
+def test_attn_pool_two_pass_kernel_on_register_shapes(gpu, case):
+    """attn_pool_regs = 0: the two-pass kernel takes the shapes the register-resident one usually does (its float4
+    path at small T and D, every row-group count of its column sums), to the same bound."""
+    try:
+        _lib.set_option("attn_pool_regs", 0)
+        _check_parity(case, "attn_pool_2pass_kernel")
+    finally:
+        _lib.set_option("attn_pool_regs", 1)
+
+
+def test_attn_pool_overflow_guard(gpu):
+    """Scores of several hundred: the softmax subtracts the row maximum, so nothing overflows."""
+    c = _case(OVERFLOW)
+    assert float((c["q"].unsqueeze(1) * c["y"]).sum(-1).abs().max()) > 300
+    outs = _raw(OVERFLOW, *_device_inputs(OVERFLOW))
+    for o in outs:
+        assert torch.isfinite(o).all()
+    assert float((outs[1].double().sum(dim=1) - 1).abs().max()) <= 1e-6
+
+
+@pytest.mark.parametrize("case", [CASES[0], CASES[4], CASES[6]])
+def test_attn_pool_is_deterministic_and_capturable(gpu, case):
+    """Two eager runs give the same bits, and so does a replay of a captured forward + backward."""
+    y, q, dctx = _device_inputs(case)
+    first = [o.clone() for o in _raw(case, y, q, dctx)]
+    second = _raw(case, y, q, dctx)
+    for a, b in zip(first, second):
+        assert torch.equal(a, b)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        _raw(case, y, q, dctx)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        outs = _raw(case, y, q, dctx)
+    for o in outs:
+        o.fill_(float("nan"))
+    graph.replay()
+    torch.cuda.synchronize()
+    for a, b in zip(first, outs):
+        assert torch.equal(a, b)
+
+
+def test_attention_pool_module_autograd(gpu):
+    case = CASES[5]
+    B, T, D, scale, _ = case
+    y, q, dctx = _device_inputs(case)
+    ctx_raw, alpha_raw, dy_raw, dq_raw = _raw(case, y, q, dctx)
+    ym, qm = y.clone().requires_grad_(True), q.clone().requires_grad_(True)
+    ctx, alpha = snn.AttentionPool()(ym, qm)    # the default scale is 1 / sqrt(D)
+    assert not alpha.requires_grad and ctx.requires_grad
+    (ctx * dctx).sum().backward()
+    assert torch.equal(ctx.detach(), ctx_raw) and torch.equal(alpha, alpha_raw)
+    assert torch.equal(ym.grad, dy_raw) and torch.equal(qm.grad, dq_raw)
+    ctx2, _ = snn.AttentionPool(scale=0.5)(y, q)
+    assert not torch.equal(ctx2, ctx_raw)
+    with pytest.raises(_lib.SrkError):
+        snn.AttentionPool()(y, q[:, :-1])
+
+
+# ----------------------------------------------------------------------------- the plugin
+H, LAYERS = 128, 1   # the GRU kernels need H % 128 == 0
+
+
+def _seeded():
+    return OM.seeded_state_dict(MfccBGRUAtt(H, LAYERS), 0)
+
+
+def test_mfcc_bgru_att_vs_float64(gpu):
+    x, lab = synthetic_clips(4, seed=11)
+    sd = _seeded()
+    ref = MfccBGRUAtt(H, LAYERS).double()
+    ref.load_state_dict(sd)
+    rout = ref(torch.from_numpy(x))
+    rloss = torch.nn.CrossEntropyLoss()(rout, torch.from_numpy(lab))
+    rloss.backward()
+    ralpha = ref.attention(torch.from_numpy(x))
+
+    net = model_mfcc_bgru_att.Network(num_features=H, num_layers=LAYERS).cuda()
+    assert set(net.state_dict()) == set(sd)
+    net.load_state_dict(sd)
+    out = net(torch.from_numpy(x))
+    loss = snn.CrossEntropyLoss()(out, torch.from_numpy(lab).cuda())
+    loss.backward()
+    assert rel_err(out.detach().cpu().numpy(), rout.detach().numpy()) <= LOGITS_REL
+    assert abs(loss.item() - rloss.item()) <= 1e-4 * max(1.0, abs(rloss.item()))
+    rgrads = dict(ref.named_parameters())
+    worst = ("", 0.0)
+    for k, p in net.named_parameters():
+        e = rel_err(p.grad.cpu().numpy(), rgrads[k].grad.numpy())
+        worst = max(worst, (k, e), key=lambda t: t[1])
+        assert e <= 2e-3, (k, e)
+    print("mfcc_bgru_att: worst gradient max-norm error %s %.3g" % worst)
+    alpha = net.attention(torch.from_numpy(x))
+    assert alpha.shape == (4, 51) and not alpha.requires_grad
+    assert float((alpha.cpu().double() - ralpha).abs().max()) <= 1e-5
+
+
+def test_mfcc_bgru_att_warm_starts_from_mfcc_bgru(gpu):
+    """A mfcc_bgru checkpoint loads with strict=False: everything but the query."""
+    from speechrecognitionproject_amd.models import model_mfcc_bgru
+    sd = model_mfcc_bgru.Network().state_dict()
+    res = model_mfcc_bgru_att.Network().load_state_dict(sd, strict=False)
+    assert sorted(res.missing_keys) == ["query.bias", "query.weight"] and not res.unexpected_keys
+
+
+def _setup(B, seed):
+    net = model_mfcc_bgru_att.Network(num_features=H, num_layers=LAYERS).cuda()
+    net.load_state_dict(_seeded())
+    net.train()
+    flat = FlatParams(net.parameters())
+    opt = Adam(net.parameters(), lr=1e-4, flat=flat)
+    x, y = synthetic_clips(3 * B, seed=seed)
+    return net, flat, opt, torch.from_numpy(x).cuda().view(3, B, -1), torch.from_numpy(y).cuda().view(3, B)
+
+
+def test_mfcc_bgru_att_graph_replay_equals_eager_steps(gpu):
+    """3 train steps replayed from one captured HIP graph == the same steps run eagerly, bit for bit (the model has
+    no dropout); an eager step launches the pool twice (forward, backward)."""
+    K, B = 3, 4
+    states = []
+    for graphed in (False, True):
+        torch.manual_seed(0)
+        net, flat, opt, pcm, lab = _setup(B, seed=23)
+        crit = snn.CrossEntropyLoss()
+        sx, sy = pcm[0].clone(), lab[0].clone()
+
+        def body():
+            opt.zero_grad()
+            loss = crit(net(sx), sy)
+            loss.backward()
+            opt.step()
+            return loss
+
+        losses = []
+        if graphed:
+            with warnings.catch_warnings(record=True) as ws:
+                warnings.simplefilter("always")
+                g = GraphedStep(body, warmup=2)
+                for i in range(K):
+                    sx.copy_(pcm[(i + 1) % 3])
+                    sy.copy_(lab[(i + 1) % 3])
+                    losses.append(g.replay().item())
+            bad = [str(w.message)[:120] for w in ws if "AccumulateGrad" in str(w.message)]
+            assert not bad, bad
+            g.release()
+        else:
+            for i in range(2 + K):
+                if i >= 2:
+                    sx.copy_(pcm[(i - 1) % 3])
+                    sy.copy_(lab[(i - 1) % 3])
+                if i == 1:
+                    _lib.prof_enable(1)
+                try:
+                    loss = body()
+                    if i == 1:
+                        torch.cuda.synchronize()
+                        assert _lib.prof_read("attn_pool")[0] == 2
+                finally:
+                    if i == 1:
+                        _lib.prof_enable(0)
+                if i >= 2:
+                    losses.append(loss.item())
+        torch.cuda.synchronize()
+        states.append((flat.data.clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone(), opt.state_dev.clone(), losses))
+    (p0, m0, v0, s0, l0), (p1, m1, v1, s1, l1) = states
+    assert int(s0[0]) == int(s1[0]) == 2 + K
+    assert all(np.isfinite(l0)) and l0 == l1
+    assert torch.equal(p0, p1) and torch.equal(m0, m1) and torch.equal(v0, v1)
+
+
+def test_mfcc_bgru_att_bf16_step(gpu):
+    """bf16 matrix-core operands around the pool: one train step stays finite and the pool (fp32 at every
+    precision) still runs under its category."""
+    try:
+        _lib.set_matmul_precision("bf16")
+        net, flat, opt, pcm, lab = _setup(4, seed=29)
+        _lib.prof_enable(1)
+        opt.zero_grad()
+        out = net(pcm[0])
+        loss = snn.CrossEntropyLoss()(out, lab[0])
+        loss.backward()
+        torch.cuda.synchronize()
+        n_pool = _lib.prof_read("attn_pool")[0]
+        opt.step()
+    finally:
+        _lib.prof_enable(0)
+        _lib.set_matmul_precision("fp32")
+    assert n_pool == 2
+    assert torch.isfinite(out).all() and np.isfinite(loss.item())
+    assert torch.isfinite(flat.grad).all() and float(flat.grad.abs().max()) > 0
+    assert all(p.grad is not None for p in net.parameters())
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16", "fp16"])
+def test_mfcc_bgru_att_training_entry_point(gpu, tmp_path, precision):
+    from speechrecognitionproject_amd.training import main
+    main(["-key", "t", "-lr", "0.0001", "--model", "mfcc_bgru_att", "--synthetic", "64", "--batch-size", "16",
+          "--precision", precision, "--output-path", str(tmp_path), "--log-every", "2", "--no-eval"])
+    losses = [float(l) for l in open(tmp_path / "loss_t.txt")]
+    assert len(losses) == 4 and all(np.isfinite(losses))   # two eager steps, the capture, two replays
