@@ -368,6 +368,14 @@ int srk_conv1_pool_fwd16(const float* x, int64_t N, int64_t H, int64_t W, const 
 int srk_conv1_pool_wgrad(const float* x, int64_t N, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW,
                          int64_t ph, int64_t pw, int64_t pool, const float* dy, const uint8_t* argmax, float* dw,
                          float* db, float* ws, void* stream);
+/* The data gradient of the same fused layer, for an input that carries a gradient (a trainable front-end such
+ * as nn.PCEN before conv1): dx [N, H, W] = conv-transpose of the pooled gradient dy routed through argmax, with
+ * the weights w [64,1,KH,KW]; gathered straight from dy and argmax (the unpooled gradient is never formed),
+ * fixed summation order, fully written.  The two fused geometries with W % pool == 0 only (SRK_ERR_INVALID
+ * else).  Profiler category "conv1_pool_dgrad".                                                          */
+int srk_conv1_pool_dgrad(const float* w, int64_t N, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW,
+                         int64_t ph, int64_t pw, int64_t pool, const float* dy, const uint8_t* argmax, float* dx,
+                         void* stream);
 int srk_maxpool_nhwc_fwd(const float* x, int64_t N, int64_t H, int64_t W, int64_t C, int64_t kh, int64_t kw,
                          float* y, void* stream);
 int srk_maxpool_nhwc_bwd(const float* x, const float* dy, int64_t N, int64_t H, int64_t W, int64_t C, int64_t kh,
@@ -509,6 +517,37 @@ int srk_attn_pool_fwd(const float* y, const float* q, int64_t B, int64_t T, int6
                       float* alpha, void* stream);
 int srk_attn_pool_bwd(const float* y, const float* q, const float* alpha, const float* dctx, int64_t B, int64_t T,
                       int64_t D, float scale, float* dy, float* dq, void* stream);
+
+/* ---------------------------------------------------------------- per-channel energy normalisation
+ * Trainable PCEN (Wang et al., ICASSP 2017; nn.PCEN over K2's [B][98][120] dB output; no reference
+ * counterpart): each band is divided by a smoothed version of its own recent energy and root-compressed,
+ * every constant learned per band.  Per clip b, frame t, channel c, raw parameters p [4][C]:
+ *   alpha = exp(p[0][c]), delta = exp(p[1][c]), r = exp(p[2][c]), s = sigmoid(p[3][c]),
+ *   E[t] = exp(log_scale * x[t]) (log_scale != 0; ln(10)/20 for dB input) or x[t] (log_scale == 0),
+ *   M[0] = E[0], M[t] = (1 - s) M[t-1] + s E[t],
+ *   u = eps + M[t], g = E[t] u^-alpha, v = g + delta, y[t] = v^r - delta^r.
+ * x / y / m / dy / dx [B][T][C] contiguous, p / dp [4][C]; fp32 at every matmul precision.
+ * Backward, dy given: dv = dy r v^(r-1); d_r = sum dy (v^r ln v - delta^r ln delta);
+ *   d_delta = sum (dv - dy r delta^(r-1)); d_alpha = sum dv g (-ln u); du = -alpha dv g / u;
+ *   reverse scan G[T] = 0, G[t] = du[t] + (1 - s) G[t+1]; dE[t] = dv u^-alpha + s G[t] (t >= 1),
+ *   dE[0] = dv u^-alpha + G[0]; d_s = sum_{t >= 1} G[t] (E[t] - M[t-1]); dx = dE E log_scale (or dE);
+ *   dp = [d_alpha alpha, d_delta delta, d_r r, d_s s (1 - s)], the sums over b and t: the gradient with
+ *   respect to the RAW parameters, written, not accumulated.
+ * One thread per (clip, channel) column.  The forward is one launch (m_out == NULL: M is not written, for
+ * evaluation); the backward is the reverse scan (dx == NULL: not written) plus one small launch that sums
+ * the columns' parameter sums in ws (srk_pcen_workspace_floats floats) over the clips and applies the chain
+ * rule.  Every sum has a fixed order and there are no floating-point atomics, so equal inputs give equal
+ * bits (eagerly and from a replayed graph).
+ * Checked on the host before any device work, SRK_ERR_INVALID with "pcen" in srk_last_error():
+ * B < 1, T outside 1..1024, C outside 1..1024, B T C >= 2^31, eps not finite or <= 0, log_scale not
+ * finite, any required pointer null.
+ * Profiler category "pcen" (one record per launch, with its algorithmic bytes).                     */
+int64_t srk_pcen_workspace_floats(int64_t B, int64_t T, int64_t C);
+int srk_pcen_fwd(const float* x, const float* p, int64_t B, int64_t T, int64_t C, float log_scale, float eps,
+                 float* y, float* m_out /* [B][T][C] or NULL */, void* stream);
+int srk_pcen_bwd(const float* x, const float* p, const float* m, const float* dy, int64_t B, int64_t T, int64_t C,
+                 float log_scale, float eps, float* dx /* or NULL */, float* dp /* [4][C], written not accumulated */,
+                 float* ws, void* stream);
 
 /* ---------------------------------------------------------------- diagnostics (tests only)
  * Directed checks of two instruction patterns (csrc/diag.hip; tests/test_diag_gpu.py):

@@ -91,6 +91,7 @@ _SIGS = {
     "srk_conv1_pool_fwd": [_P, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P],
     "srk_conv1_pool_fwd16": [_P, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P],
     "srk_conv1_pool_wgrad": [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P],
+    "srk_conv1_pool_dgrad": [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P],
     "srk_maxpool_nhwc_fwd": [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P],
     "srk_maxpool_nhwc_bwd": [_P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P],
     "srk_batchnorm_fwd": [_P, _I64, _I64, _P, _P, _F, _F, _I, _P, _P, _P, _I, _P, _P, _P, _P],
@@ -119,10 +120,14 @@ _SIGS = {
     "srk_dropout_apply": [_P, _P, _I64, _F, _P, _P],
     "srk_attn_pool_fwd": [_P, _P, _I64, _I64, _I64, _F, _P, _P, _P],
     "srk_attn_pool_bwd": [_P, _P, _P, _P, _I64, _I64, _I64, _F, _P, _P, _P],
+    "srk_pcen_workspace_floats": [_I64, _I64, _I64],
+    "srk_pcen_fwd": [_P, _P, _I64, _I64, _I64, _F, _F, _P, _P, _P],
+    "srk_pcen_bwd": [_P, _P, _P, _P, _I64, _I64, _I64, _F, _F, _P, _P, _P, _P],
 }
 _RESTYPE = {"srk_last_error": ctypes.c_char_p, "srk_spin_timeouts": ctypes.c_int64, "srk_scratch_generation": ctypes.c_int64, "srk_gru_workspace_floats": ctypes.c_int64, "srk_gru_y16_offset": ctypes.c_int64,
             "srk_conv2d_workspace_floats": ctypes.c_int64, "srk_conv1_pool_workspace_floats": ctypes.c_int64,
-            "srk_pitch_workspace_bytes": ctypes.c_int64, "srk_source_stamp": ctypes.c_char_p}
+            "srk_pitch_workspace_bytes": ctypes.c_int64, "srk_source_stamp": ctypes.c_char_p,
+            "srk_pcen_workspace_floats": ctypes.c_int64}
 
 
 class SrkError(RuntimeError):

@@ -14,7 +14,13 @@
 //            so dW[co][kh][kw] = sum_q dP[q][co] * x[pixel*(q, co) + tap] and db[co] = sum_q dP[q][co]
 //            are accumulated straight from dP — the dense 1.5 GB unpooled gradient is never formed.
 //            Per-block partial sums are reduced in a fixed order (deterministic).
-// The input needs no gradient (it is the feature tensor, computed under no_grad).
+// The input usually needs no gradient (it is the feature tensor, computed under no_grad).  Behind a trainable
+// front-end (nn.PCEN in model_fbanks_cnn_pcen) it does:
+// Data gradient: dX[h][w] = sum over (co, kh, kw) of W[co][kh][kw] * dU[h + ph - kh][w + pw - kw][co] with dU the
+//            pooled gradient at its argmax — gathered straight from dP and the argmax (a pool window of outputs
+//            reads source windows q - 1, q, q + 1 of KH rows), 4 channels per lane, the 16 lanes of a window
+//            summed by xor-shuffles in a fixed order.  The generic implicit-GEMM data gradient pads the single
+//            input channel to a full tile (13 ms at cfg3 against 0.3 ms for this layer's other two kernels).
 #include "srk_internal.h"
 
 namespace srk {
@@ -47,6 +53,7 @@ struct C1Args {
   const float* dy;     // bwd: pooled gradient [N][H][W/PW][64]
   float* partial;      // bwd: [blocks][64 * (KH*KW + 1)]
   unsigned short* y16; // fwd (16-bit matmul modes, optional): the pooled activation's 16-bit operand copy
+  float* dx;           // data gradient [N][H][W]
 };
 
 typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
@@ -233,6 +240,81 @@ __global__ __launch_bounds__(256) void conv1_pool_wgrad_kernel(C1Args a) {
   }
 }
 
+constexpr int kRowsD = 8;            // image rows per block of the data gradient
+
+// Same-padded geometries only (ph = (KH - 1) / 2, pw = (KW - 1) / 2; both fused ones are) with W % PW == 0: every
+// input column then lies in a pool window, and a window of PW outputs reads the source windows q - 1, q, q + 1.
+template <int KH, int KW, int PW>
+__global__ __launch_bounds__(256) void conv1_pool_dgrad_kernel(C1Args a) {
+  constexpr int T = KH * KW, PH = (KH - 1) / 2, PWD = (KW - 1) / 2;
+  static_assert(PWD <= PW && KW - 1 - PWD <= PW, "a window of outputs reads its two neighbour windows at most");
+  const int c4 = threadIdx.x % kC4, pg = threadIdx.x / kC4;
+  const int hp = (a.H + kRowsD - 1) / kRowsD;
+  const int n = blockIdx.x / hp, h0 = (blockIdx.x % hp) * kRowsD;
+  v4f wr[T];
+#pragma unroll
+  for (int t = 0; t < T; ++t)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) wr[t][e] = a.w[(c4 * 4 + e) * T + t];
+  const int Wq = a.W / PW;
+  const int rows = min(kRowsD, a.H - h0);
+  for (int wi = pg; wi < rows * Wq; wi += kPG) {   // (the 16 lanes of a window share pg: they leave together)
+    const int h = h0 + wi / Wq, q = wi % Wq;
+    float out[PW];
+#pragma unroll
+    for (int j = 0; j < PW; ++j) out[j] = 0.f;
+    // every source quad and argmax word of the window is requested before the first is used (rows and windows
+    // outside the image: a clamped, in-bounds address, the gradient zeroed) — with the loads inside the tap loops'
+    // bounds branches the kernel waited out 21 round trips per window (2.3 ms at cfg3)
+    v4f gs[KH][3];
+    unsigned is[KH][3];
+#pragma unroll
+    for (int kh = 0; kh < KH; ++kh) {
+      const int hs = h + PH - kh;   // the conv output row whose tap kh reads input row h
+      const bool hok = hs >= 0 && hs < a.H;
+      const int hc = min(max(hs, 0), a.H - 1);
+#pragma unroll
+      for (int d = -1; d <= 1; ++d) {
+        const int qs = q + d;
+        const bool ok = hok && qs >= 0 && qs < Wq;
+        const size_t o = (((size_t)n * a.H + hc) * Wq + min(max(qs, 0), Wq - 1)) * kCo + c4 * 4;
+        const v4f g = *reinterpret_cast<const v4f*>(a.dy + o);
+        gs[kh][d + 1] = ok ? g : v4f{0.f, 0.f, 0.f, 0.f};
+        is[kh][d + 1] = *reinterpret_cast<const unsigned*>(a.arg + o);
+      }
+    }
+#pragma unroll
+    for (int kh = 0; kh < KH; ++kh) {
+#pragma unroll
+      for (int d = -1; d <= 1; ++d) {
+        const v4f g = gs[kh][d + 1];
+        const unsigned idx = is[kh][d + 1];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int p = (int)((idx >> (8 * e)) & 0xFFu);
+#pragma unroll
+          for (int j = 0; j < PW; ++j)
+#pragma unroll
+            for (int kw = 0; kw < KW; ++kw) {
+              // output column q PW + j reads conv output column (q PW + j) + PWD - kw = qs PW + pn through tap kw
+              const int pn = -d * PW + j + PWD - kw;
+              if (pn >= 0 && pn < PW) out[j] = fmaf(p == pn ? g[e] : 0.f, wr[kh * KW + kw][e], out[j]);
+            }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < PW; ++j) {
+      float v = out[j];
+      v += __shfl_xor(v, 1, 64);
+      v += __shfl_xor(v, 2, 64);
+      v += __shfl_xor(v, 4, 64);
+      v += __shfl_xor(v, 8, 64);
+      if (c4 == 0) a.dx[((size_t)n * a.H + h) * a.W + q * PW + j] = v;
+    }
+  }
+}
+
 // dw[co][t] = sum over blocks; db[co] likewise.  A workgroup owns 64 outputs (lane = output); its 16
 // waves each sum a contiguous run of blocks (8 loads in flight per lane), then the 16 wave sums are
 // added in wave order through LDS — a fixed order (deterministic), and 16 x shorter chains than one
@@ -366,6 +448,32 @@ int srk_conv1_pool_wgrad(const float* x, int64_t N, int64_t H, int64_t W, int64_
   const int per = (int)(Co * (T + 1));
   hipLaunchKernelGGL(srk::conv1_pool_reduce_kernel, dim3((unsigned)((per + 63) / 64)), dim3(64 * srk::kRedWaves), 0, s,
                      ws, blocks, T, dw, db);
+  SRK_CHECK_HIP(hipGetLastError());
+  return SRK_OK;
+  SRK_API_END
+}
+
+int srk_conv1_pool_dgrad(const float* w, int64_t N, int64_t H, int64_t W, int64_t Co, int64_t KH, int64_t KW,
+                         int64_t ph, int64_t pw, int64_t pool, const float* dy, const uint8_t* argmax, float* dx,
+                         void* stream) {
+  SRK_API_BEGIN
+  if (int rc = srk::check_c1(N, H, W, Co, KH, KW, ph, pw, pool)) return rc;
+  SRK_REQUIRE(W % pool == 0, SRK_ERR_INVALID, "conv1_pool_dgrad: W %lld is not a multiple of the pool width %lld",
+              (long long)W, (long long)pool);
+  SRK_REQUIRE(w && dy && argmax && dx, SRK_ERR_INVALID, "conv1_pool_dgrad: null pointer");
+  SRK_REQUIRE((uintptr_t)dy % 16 == 0 && (uintptr_t)argmax % 4 == 0, SRK_ERR_INVALID,
+              "conv1_pool_dgrad: misaligned gradient or argmax");
+  srk::C1Args a{};
+  a.N = (int)N; a.H = (int)H; a.W = (int)W; a.ph = (int)ph; a.pw = (int)pw;
+  a.w = w; a.dy = dy; a.arg = const_cast<uint8_t*>(argmax); a.dx = dx;
+  hipStream_t s = srk::as_stream(stream);
+  const int hp = (int)((H + srk::kRowsD - 1) / srk::kRowsD);
+  // algorithmic: the pooled gradient and argmax once + the image gradient
+  srk::ProfScope prof("conv1_pool_dgrad", s, 4.0 * N * H * W + 5.0 * N * H * (W / pool) * Co);
+  prof.detail("conv1_pool_dgrad_valu<%lldx%lld,pool%lld>", (long long)KH, (long long)KW, (long long)pool);
+  const dim3 g((unsigned)(N * hp));
+  if (KH == 7) hipLaunchKernelGGL((srk::conv1_pool_dgrad_kernel<7, 3, 3>), g, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((srk::conv1_pool_dgrad_kernel<3, 7, 5>), g, dim3(256), 0, s, a);
   SRK_CHECK_HIP(hipGetLastError());
   return SRK_OK;
   SRK_API_END

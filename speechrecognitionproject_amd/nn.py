@@ -6,6 +6,7 @@ Every forward/backward runs a HIP kernel through the C ABI; there is no CPU or t
 fallback (the GPU and the library are required).
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -241,6 +242,84 @@ class AttentionPool(tnn.Module):
         require_gpu()
         scale = float(self.scale) if self.scale is not None else y.shape[-1] ** -0.5
         return _AttentionPoolFn.apply(y, q, scale)
+
+
+# ----------------------------------------------------------------------------- PCEN
+class _PCENFn(torch.autograd.Function):
+    """srk_pcen_fwd / _bwd (include/srk.h): fp32 at every matmul precision.  The gradient of ``params`` is with
+    respect to the raw rows (the library applies exp' / sigmoid'), returned to autograd."""
+
+    @staticmethod
+    def forward(ctx, x, params, log_scale, eps, grad_on, ws):
+        # grad_on: torch.is_grad_enabled() at the call (always off in here): evaluation passes keep no M
+        x, p = x.contiguous(), params.contiguous()
+        _check_cuda(x, p)
+        if x.dim() != 3 or p.shape != (4, x.shape[2]):
+            raise _lib.SrkError("PCEN: x must be [B, T, C] and params [4, C], got %s and %s"
+                                % (tuple(x.shape), tuple(p.shape)))
+        B, T, C = x.shape
+        y = torch.empty_like(x)
+        m = torch.empty_like(x) if grad_on and any(ctx.needs_input_grad[:2]) else None
+        call("srk_pcen_fwd", ptr(x), ptr(p), B, T, C, log_scale, eps, ptr(y), ptr(m) if m is not None else None,
+             stream_ptr())
+        if m is not None:
+            ctx.save_for_backward(x, p, m)
+        ctx.consts = (log_scale, eps, ws)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, p, m = ctx.saved_tensors
+        log_scale, eps, ws = ctx.consts
+        B, T, C = x.shape
+        dy = dy.contiguous()
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dp = torch.empty_like(p)
+        call("srk_pcen_bwd", ptr(x), ptr(p), ptr(m), ptr(dy), B, T, C, log_scale, eps,
+             ptr(dx) if dx is not None else None, ptr(dp), ptr(ws), stream_ptr())
+        return dx, dp, None, None, None, None
+
+
+class PCEN(tnn.Module):
+    """Trainable per-channel energy normalisation (Wang et al., ICASSP 2017) over ``x [B, T, C]``:
+    ``E = exp(log_scale x)`` (``log_scale`` 0: ``E = x``), ``M[0] = E[0]``, ``M[t] = (1 - s) M[t-1] + s E[t]``,
+    ``y = (E / (eps + M)^alpha + delta)^r - delta^r``, one fused kernel each way.  ``log_scale`` defaults to
+    ln(10) / 20, the inverse of K2's ``20 log10``; 1 serves K3's natural log.
+
+    One parameter ``params`` [4, C]: rows log alpha, log delta, log r, logit s (so every constant keeps its
+    sign and s stays in (0, 1) under any optimizer step), initialised from the constructor's values, the
+    paper's.  ``constants()`` returns the effective per-channel vectors."""
+
+    def __init__(self, num_channels, log_scale=math.log(10.0) / 20.0, eps=1e-6, alpha=0.98, delta=2.0, r=0.5, s=0.025):
+        super().__init__()
+        if not (alpha > 0 and delta > 0 and r > 0 and 0 < s < 1 and eps > 0):
+            raise ValueError("PCEN needs alpha, delta, r, eps > 0 and 0 < s < 1")
+        self.num_channels, self.log_scale, self.eps = int(num_channels), float(log_scale), float(eps)
+        rows = torch.tensor([math.log(alpha), math.log(delta), math.log(r), math.log(s / (1.0 - s))],
+                            dtype=torch.float64)
+        self.params = tnn.Parameter(rows.unsqueeze(1).repeat(1, self.num_channels).float())
+        self._ws = {}
+
+    def constants(self):
+        """{"alpha", "delta", "r", "s"}: the effective per-channel constants, detached [C] tensors."""
+        with torch.no_grad():
+            p = self.params.detach()
+            return {"alpha": p[0].exp(), "delta": p[1].exp(), "r": p[2].exp(), "s": torch.sigmoid(p[3])}
+
+    def _workspace(self, x):
+        # one buffer per (device, shape), kept for the module's life: a captured step keeps its address
+        key = (x.device.index,) + tuple(x.shape)
+        ws = self._ws.get(key)
+        if ws is None:
+            n = int(_lib.lib().srk_pcen_workspace_floats(*x.shape))
+            ws = self._ws[key] = torch.empty(n, device=x.device)
+        return ws
+
+    def forward(self, x):
+        require_gpu()
+        grad_on = torch.is_grad_enabled()
+        ws = self._workspace(x) if grad_on and x.dim() == 3 else None
+        return _PCENFn.apply(x, self.params, self.log_scale, self.eps, grad_on, ws)
 
 
 # ----------------------------------------------------------------------------- Linear
@@ -584,7 +663,8 @@ def conv1d_nlc(x, weight, bias=None, stride=1, padding=0, dilation=1):
 
 class _Conv1PoolFn(torch.autograd.Function):
     """conv1 + bias + MaxPool2d((1, pool)) of model_fbanks_cnn / model_spec_cnn (srk_conv1_pool_fwd /
-    _wgrad): one input channel, the pooled NHWC output; the input (features) gets no gradient."""
+    _wgrad / _dgrad): one input channel, the pooled NHWC output; the input gets a gradient only when it carries one
+    (features behind a trainable front-end such as PCEN)."""
 
     @staticmethod
     def forward(ctx, x, w, b, padding, pool, y16_only=False):
@@ -606,32 +686,40 @@ class _Conv1PoolFn(torch.autograd.Function):
              pool, ptr(y), ptr(arg), ptr(y16) if y16 is not None else None, ctypes.byref(written), stream_ptr())
         if written.value:
             _copy16_put(y, y16)
-        ctx.save_for_backward(x, arg)
+        ctx.save_for_backward(x, arg, w)
         ctx.geom = (Co, KH, KW, padding, pool)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, arg = ctx.saved_tensors
+        x, arg, w = ctx.saved_tensors
         Co, KH, KW, padding, pool = ctx.geom
         N, H, W = x.shape
+        dy = dy.contiguous()
         dw = torch.empty((Co, 1, KH, KW), device=x.device)
         db = torch.empty((Co,), device=x.device)
         ws = torch.empty(int(_lib.lib().srk_conv1_pool_workspace_floats(Co, KH, KW)), device=x.device)
-        call("srk_conv1_pool_wgrad", ptr(x), N, H, W, Co, KH, KW, padding[0], padding[1], pool, ptr(dy.contiguous()),
+        call("srk_conv1_pool_wgrad", ptr(x), N, H, W, Co, KH, KW, padding[0], padding[1], pool, ptr(dy),
              ptr(arg), ptr(dw), ptr(db), ptr(ws), stream_ptr())
-        return None, dw, db, None, None, None
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            call("srk_conv1_pool_dgrad", ptr(w.contiguous()), N, H, W, Co, KH, KW, padding[0], padding[1], pool,
+                 ptr(dy), ptr(arg), ptr(dx), stream_ptr())
+        return dx, dw, db, None, None, None
 
 
 def conv1_pool(x, conv, pool, next_conv_pool16=False):
     """Fused ``pool(conv(x))`` for a one-channel NHW input when the geometry is the one
-    srk_conv1_pool supports (conv1 + maxpool1 of model_fbanks_cnn / model_spec_cnn) and ``x`` needs
-    no gradient; otherwise the separate conv and pool kernels.  Returns NHWC.
+    srk_conv1_pool supports (conv1 + maxpool1 of model_fbanks_cnn / model_spec_cnn; an ``x`` that carries a
+    gradient also needs a width that is a multiple of the pool's); otherwise the separate conv and pool kernels.
+    Returns NHWC.
     next_conv_pool16: the result goes straight into ``conv_pool`` (fbanks_cnn conv2): in a 16-bit training
     step with 16-bit conv forwards that reads only the 16-bit copy, so the fp32 activation is not stored."""
     geom = (tuple(conv.kernel_size), tuple(conv.padding), tuple(pool.kernel_size))
     if (conv.in_channels == 1 and conv.out_channels == 64 and tuple(conv.stride) == (1, 1) and conv.bias is not None
-            and geom in (((7, 3), (3, 1), (1, 3)), ((3, 7), (1, 3), (1, 5))) and not x.requires_grad):
+            and geom in (((7, 3), (3, 1), (1, 3)), ((3, 7), (1, 3), (1, 5)))
+            and (not x.requires_grad or x.shape[-1] % pool.kernel_size[1] == 0)):
         require_gpu()
         y16_only = bool(next_conv_pool16 and _lib.fused_conv_pool() and not _lib.option("conv_fwd_fp32"))
         return _Conv1PoolFn.apply(x, conv.weight, conv.bias, conv.padding, pool.kernel_size[1], y16_only)
