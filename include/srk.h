@@ -20,7 +20,7 @@
 
 #include <stdint.h>
 
-#define SRK_ABI_VERSION 2
+#define SRK_ABI_VERSION 3
 
 #ifdef __cplusplus
 extern "C" {
@@ -278,7 +278,7 @@ int srk_gru_layer_bwd_x16(const float* x, const void* x16, int64_t B, int64_t T,
                           float* ws, void* stream);
 
 /* ---------------------------------------------------------------- K6: convolution / pooling
- * nn.Conv2d / nn.Conv1d (zero padding ph/pw, stride sh/sw, no groups; dilation: srk_conv1d_nlc_dil_*) as implicit GEMM
+ * nn.Conv2d / nn.Conv1d (zero padding ph/pw, stride sh/sw, no groups — depthwise: srk_dwconv2d_nhwc_*; dilation: srk_conv1d_nlc_dil_*) as implicit GEMM
  * on CHANNELS-LAST activations: x [N][H][W][Ci], y [N][Ho][Wo][Co], Ho = (H + 2ph - KH)/sh + 1.
  * Weights stay in torch layout w [Co][Ci][KH][KW] (the state_dict tensor), bias [Co] (nullable).
  * ws: srk_conv2d_workspace_floats() floats (re-laid-out weights).  The 1-D convolutions of
@@ -548,6 +548,43 @@ int srk_pcen_fwd(const float* x, const float* p, int64_t B, int64_t T, int64_t C
 int srk_pcen_bwd(const float* x, const float* p, const float* m, const float* dy, int64_t B, int64_t T, int64_t C,
                  float log_scale, float eps, float* dx /* or NULL */, float* dp /* [4][C], written not accumulated */,
                  float* ws, void* stream);
+
+/* ---------------------------------------------------------------- depthwise convolution / global average pool
+ * The two primitives of a depthwise-separable CNN block that K6 lacks (nn.DepthwiseConv2d, nn.GlobalAvgPool2d; the
+ * fbanks_dscnn plugin; no reference counterpart).  All tensors fp32, channels-last, contiguous; fp32 arithmetic at
+ * every matmul precision (there is no GEMM in a depthwise conv).  Lanes run along C: 16-byte loads / stores of 4
+ * channels when C % 4 == 0 and the pointers are 16-byte aligned, a scalar path otherwise (csrc/dwconv.hip).
+ *
+ * Depthwise nn.Conv2d (groups = C, channel multiplier 1, zero padding, no dilation):
+ * x [N][H][W][C], w [C][1][KH][KW] (the torch state_dict tensor), bias [C] nullable,
+ * y [N][Ho][Wo][C], Ho = (H + 2ph - KH)/sh + 1, Wo likewise:
+ *   y[n][ho][wo][c] = bias[c] + sum_{kh,kw} w[c][kh][kw] x[n][ho sh - ph + kh][wo sw - pw + kw][c].
+ * Backward: dx (NULL: not computed) in the gather form — every element sums the taps whose output position
+ * exists, written once in full, no zero fill, no atomics; dw[c][kh][kw] = sum_{n,ho,wo} dy x and
+ * db[c] = sum dy (NULL: not written) as per-thread register partials, a per-workgroup LDS sum, per-workgroup
+ * slabs in ws (srk_dwconv2d_workspace_floats floats) and a second launch that sums the slabs in a fixed order;
+ * with dw_accumulate != 0 that launch ADDS into dw (a FlatParams-owned .grad, the convention of
+ * srk_conv2d_nhwc_bwd16_acc), otherwise it writes it; db is always written.  Equal inputs give equal bits.
+ * Domain: 1 <= KH, KW <= 7; sh, sw in {1, 2}; 0 <= ph < KH, 0 <= pw < KW; Ho, Wo >= 1; N, H, W, C >= 1; every
+ * tensor below 2^31 elements.  Anything else, a null required pointer or a null ws is refused on the host before
+ * any device work: SRK_ERR_INVALID with "dwconv" in srk_last_error() (srk_dwconv2d_workspace_floats returns 0).
+ *
+ * Global average pool: x [N][HW][C] -> y [N][C] = the mean over the HW positions of each clip (summed in a fixed
+ * order, divided by HW); dx = dy / HW broadcast.  N, HW, C >= 1, N HW C < 2^31, else SRK_ERR_INVALID with
+ * "avgpool" in srk_last_error().
+ * Every launch is on the given stream, with no host synchronisation and no allocation.
+ * Profiler categories "dwconv_fwd", "dwconv_dgrad", "dwconv_wgrad" (both launches) and "avgpool".       */
+int64_t srk_dwconv2d_workspace_floats(int64_t N, int64_t H, int64_t W, int64_t C, int64_t KH, int64_t KW,
+                                      int64_t ph, int64_t pw, int64_t sh, int64_t sw);
+int srk_dwconv2d_nhwc_fwd(const float* x, int64_t N, int64_t H, int64_t W, int64_t C, const float* w,
+                          const float* bias, int64_t KH, int64_t KW, int64_t ph, int64_t pw, int64_t sh, int64_t sw,
+                          float* y, void* stream);
+int srk_dwconv2d_nhwc_bwd(const float* x, int64_t N, int64_t H, int64_t W, int64_t C, const float* w,
+                          int64_t KH, int64_t KW, int64_t ph, int64_t pw, int64_t sh, int64_t sw, const float* dy,
+                          float* dx /* or NULL */, float* dw, float* db /* or NULL */, float* ws,
+                          int dw_accumulate, void* stream);
+int srk_avgpool_nhwc_fwd(const float* x, int64_t N, int64_t HW, int64_t C, float* y, void* stream);
+int srk_avgpool_nhwc_bwd(const float* dy, int64_t N, int64_t HW, int64_t C, float* dx, void* stream);
 
 /* ---------------------------------------------------------------- diagnostics (tests only)
  * Directed checks of two instruction patterns (csrc/diag.hip; tests/test_diag_gpu.py):

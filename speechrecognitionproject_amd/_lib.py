@@ -13,7 +13,7 @@ import torch  # noqa: F401  (load torch's HIP runtime before libsrk.so)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SRK_LIB") or os.path.join(_HERE, "libsrk.so")   # SRK_LIB: experiment builds
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "srk.h")
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -123,11 +123,17 @@ _SIGS = {
     "srk_pcen_workspace_floats": [_I64, _I64, _I64],
     "srk_pcen_fwd": [_P, _P, _I64, _I64, _I64, _F, _F, _P, _P, _P],
     "srk_pcen_bwd": [_P, _P, _P, _P, _I64, _I64, _I64, _F, _F, _P, _P, _P, _P],
+    "srk_dwconv2d_workspace_floats": [_I64] * 10,
+    "srk_dwconv2d_nhwc_fwd": [_P, _I64, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P],
+    "srk_dwconv2d_nhwc_bwd": [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P,
+                              _I, _P],
+    "srk_avgpool_nhwc_fwd": [_P, _I64, _I64, _I64, _P, _P],
+    "srk_avgpool_nhwc_bwd": [_P, _I64, _I64, _I64, _P, _P],
 }
 _RESTYPE = {"srk_last_error": ctypes.c_char_p, "srk_spin_timeouts": ctypes.c_int64, "srk_scratch_generation": ctypes.c_int64, "srk_gru_workspace_floats": ctypes.c_int64, "srk_gru_y16_offset": ctypes.c_int64,
             "srk_conv2d_workspace_floats": ctypes.c_int64, "srk_conv1_pool_workspace_floats": ctypes.c_int64,
             "srk_pitch_workspace_bytes": ctypes.c_int64, "srk_source_stamp": ctypes.c_char_p,
-            "srk_pcen_workspace_floats": ctypes.c_int64}
+            "srk_pcen_workspace_floats": ctypes.c_int64, "srk_dwconv2d_workspace_floats": ctypes.c_int64}
 
 
 class SrkError(RuntimeError):

@@ -20,6 +20,16 @@ def filter_banks(sample):
     return features.fbank(sample.reshape(1, -1))[0].cpu()
 
 
+def check_vtlp(vtlp):
+    """The constructor argument ``vtlp`` of the filter-bank plugins as ``(lo, hi)`` floats, or None."""
+    if vtlp is None:
+        return None
+    lo, hi = (float(v) for v in vtlp)
+    if not 0.8 <= lo <= hi <= 1.25:
+        raise ValueError("vtlp=(lo, hi) must satisfy 0.8 <= lo <= hi <= 1.25, got %r" % (vtlp,))
+    return (lo, hi)
+
+
 class Network(nn.Module):
     """``vtlp=(lo, hi)`` turns on the reference's VTLP augmentation (legacy/model_8/dataset_top.py:245-267:
     the mel filter bank warped by one uniform(lo, hi) factor per clip) for training-mode forwards;
@@ -30,12 +40,7 @@ class Network(nn.Module):
 
     def __init__(self, vtlp=None):
         super().__init__()
-        if vtlp is not None:
-            lo, hi = (float(v) for v in vtlp)
-            if not 0.8 <= lo <= hi <= 1.25:
-                raise ValueError("vtlp=(lo, hi) must satisfy 0.8 <= lo <= hi <= 1.25, got %r" % (vtlp,))
-            vtlp = (lo, hi)
-        self.vtlp = vtlp
+        self.vtlp = check_vtlp(vtlp)
         self.last_alpha = None
         self._alpha_bufs = {}
         self.conv1 = Conv2d(1, 64, kernel_size=(7, 3), padding=(3, 1))

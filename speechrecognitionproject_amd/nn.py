@@ -840,6 +840,105 @@ class MaxPool1d(tnn.Module):
         return y.reshape(N, L // self.kernel_size, C)
 
 
+# ----------------------------------------------------------------------------- depthwise conv / global average pool
+class _DepthwiseConv2dFn(torch.autograd.Function):
+    """srk_dwconv2d_nhwc_fwd / _bwd (include/srk.h): fp32 at every matmul precision, _Conv2dNHWCFn's conventions (the
+    weight gradient ADDED into a FlatParams-owned .grad by the kernel that forms it, dx only when needed)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, padding, stride):
+        x = x.contiguous()
+        w_param = w
+        w = w.contiguous()
+        _check_cuda(x, w, b)
+        if x.dim() != 4 or w.dim() != 4 or w.shape[0] != x.shape[3] or w.shape[1] != 1:
+            raise _lib.SrkError("depthwise conv: x must be [N, H, W, C] and the weight [C, 1, KH, KW], got %s and %s"
+                                % (tuple(x.shape), tuple(w.shape)))
+        N, H, W, C = x.shape
+        _, _, KH, KW = w.shape
+        (ph, pw), (sh, sw) = padding, stride
+        Ho, Wo = (H + 2 * ph - KH) // sh + 1, (W + 2 * pw - KW) // sw + 1
+        y = torch.empty((N, max(Ho, 0), max(Wo, 0), C), device=x.device)
+        call("srk_dwconv2d_nhwc_fwd", ptr(x), N, H, W, C, ptr(w), ptr(b) if b is not None else None, KH, KW, ph, pw,
+             sh, sw, ptr(y), stream_ptr())
+        ctx.save_for_backward(x, w)
+        ctx.w_param = w_param
+        ctx.geom = (padding, stride, b is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        (ph, pw), (sh, sw), has_b = ctx.geom
+        N, H, W, C = x.shape
+        _, _, KH, KW = w.shape
+        dy = dy.contiguous()
+        _copy16_drop(dy)   # the producing BatchNorm backward's 16-bit copy of dY, which only a dense conv reads
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gw = _flat_grad(ctx.w_param) if ctx.needs_input_grad[1] and INPLACE_GRADS else None
+        dw = gw if gw is not None else torch.empty_like(w)
+        db = torch.empty((C,), device=x.device) if has_b else None
+        ws = torch.empty(int(_lib.lib().srk_dwconv2d_workspace_floats(N, H, W, C, KH, KW, ph, pw, sh, sw)),
+                         device=x.device)
+        call("srk_dwconv2d_nhwc_bwd", ptr(x), N, H, W, C, ptr(w), KH, KW, ph, pw, sh, sw, ptr(dy),
+             ptr(dx) if dx is not None else None, ptr(dw), ptr(db) if db is not None else None, ptr(ws),
+             1 if gw is not None else 0, stream_ptr())
+        if gw is not None:
+            red = _reducer_of(ctx.w_param)
+            if red is not None:
+                red.mark_ready([ctx.w_param])
+            dw = None
+        return dx, dw, db, None, None
+
+
+class DepthwiseConv2d(tnn.Module):
+    """nn.Conv2d(C, C, kernel_size, groups=C)-compatible parameters (weight [C, 1, KH, KW], bias [C], torch init)
+    applied to CHANNELS-LAST input [N, H, W, C] -> [N, Ho, Wo, C]: one filter per channel, no mixing across channels
+    (srk_dwconv2d_nhwc_*: 1 <= KH, KW <= 7, strides 1 or 2, padding below the kernel size)."""
+
+    def __init__(self, channels, kernel_size, stride=1, padding=0, bias=True):
+        super().__init__()
+        ref = tnn.Conv2d(channels, channels, kernel_size, stride=stride, padding=padding, groups=channels, bias=bias)
+        self.channels = channels
+        self.kernel_size, self.stride, self.padding = ref.kernel_size, ref.stride, ref.padding
+        self.weight = tnn.Parameter(ref.weight.detach().clone())
+        self.bias = tnn.Parameter(ref.bias.detach().clone()) if bias else None
+
+    def forward(self, x):
+        require_gpu()
+        return _DepthwiseConv2dFn.apply(x, self.weight, self.bias, self.padding, self.stride)
+
+
+class _GlobalAvgPoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        _check_cuda(x)
+        N, C = x.shape[0], x.shape[-1]
+        HW = x.numel() // max(N * C, 1)
+        y = torch.empty((N, C), device=x.device)
+        call("srk_avgpool_nhwc_fwd", ptr(x), N, HW, C, ptr(y), stream_ptr())
+        ctx.shape = tuple(x.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        N, C = ctx.shape[0], ctx.shape[-1]
+        dx = torch.empty(ctx.shape, device=dy.device)
+        call("srk_avgpool_nhwc_bwd", ptr(dy.contiguous()), N, dx.numel() // (N * C), C, ptr(dx), stream_ptr())
+        return dx
+
+
+class GlobalAvgPool2d(tnn.Module):
+    """The mean over H and W of channels-last input: [N, H, W, C] -> [N, C] (nn.AdaptiveAvgPool2d(1) + flatten)."""
+
+    def forward(self, x):
+        require_gpu()
+        if x.dim() != 4:
+            raise _lib.SrkError("GlobalAvgPool2d: x must be [N, H, W, C], got %s" % (tuple(x.shape),))
+        return _GlobalAvgPoolFn.apply(x)
+
+
 _DROPOUT_STATE = {}   # device index -> int64[2] {base seed, call counter} read by srk_dropout_fwd_state
 _MASK63 = (1 << 63) - 1
 _DROPOUT_REPLAY = [0]

@@ -24,9 +24,10 @@ the device counter on top of the last eager seed, so masks (not the arithmetic) 
 ``--no-graph``.  ``--precision bf16|fp16`` runs the matrix cores on 16-bit operands (fp32
 accumulation, fp32 parameters); fp16 trains with a loss scale (``--loss-scale``: dynamic by
 default, or a fixed number) and skips any step whose gradients overflowed (optim.LossScaler).
-``--vtlp LO,HI`` (fbanks_cnn and fbanks_cnn_pcen, off by default) warps each training clip's mel filter bank by a
+``--vtlp LO,HI`` (fbanks_cnn, fbanks_cnn_pcen and fbanks_dscnn, off by default) warps each training clip's mel filter bank by a
 factor drawn on the device (legacy/model_8/dataset_top.py:245-267); the draw's counter lives on the
-device too, so replayed and eager steps draw the same sequence.
+device too, so replayed and eager steps draw the same sequence.  ``--model fbanks_dscnn`` is the small-footprint
+depthwise-separable CNN on the same filter banks (models/model_fbanks_dscnn.py).
 """
 import argparse
 import importlib
@@ -43,7 +44,7 @@ from .nn import CrossEntropyLoss
 from .optim import Adam, FlatParams, LossScaler
 
 PLUGINS = ("mfcc_bgru", "fbanks_cnn", "spec_bgru", "resnet_bgru", "mfrn_bgru", "cnn_bgru", "spec_cnn", "resnet_dconv",
-           "mfcc_bgru_att", "fbanks_cnn_pcen")
+           "mfcc_bgru_att", "fbanks_cnn_pcen", "fbanks_dscnn")
 
 
 def parse(argv=None):
@@ -89,13 +90,13 @@ def parse(argv=None):
                    help="write model.state_dict() to OUTPUT/models/model_KEY.ckpt after training (the reference's "
                         "checkpoint path, training.py:104-107)")
     p.add_argument('--vtlp', default=None, metavar='LO,HI',
-                   help="fbanks_cnn, fbanks_cnn_pcen: warp each training clip's mel filter bank by a factor drawn uniformly from "
+                   help="fbanks_cnn, fbanks_cnn_pcen, fbanks_dscnn: warp each training clip's mel filter bank by a factor drawn uniformly from "
                         "[LO, HI) (vocal-tract-length perturbation, the reference's legacy/model_8 trains with "
                         "0.9,1.1); off by default")
     args = p.parse_args(argv)
     if args.vtlp is not None:
-        if args.model not in ('fbanks_cnn', 'fbanks_cnn_pcen'):
-            p.error('--vtlp applies to --model fbanks_cnn and fbanks_cnn_pcen only')
+        if args.model not in ('fbanks_cnn', 'fbanks_cnn_pcen', 'fbanks_dscnn'):
+            p.error('--vtlp applies to --model fbanks_cnn, fbanks_cnn_pcen and fbanks_dscnn only')
         try:
             lo, hi = (float(v) for v in args.vtlp.split(','))
         except ValueError:
