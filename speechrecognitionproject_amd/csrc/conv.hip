@@ -2643,8 +2643,6 @@ __global__ __launch_bounds__(256, 1) void conv_row16_dgrad_kernel(RowDgArgs a) {
   }
 }
 
-// The ring conv when the shape qualifies (fp32 operands, option conv_ring, channel-aligned, stride 1
-// for the data gradient, 32-bit byte offsets); returns 1 if it did not run.
 // Algorithmic HBM bytes of one implicit-GEMM conv launch (ProfScope::bytes): the two operand tensors read once
 // at their element size in HBM (esz: 2 for 16-bit sources, 4 otherwise) and the output written once in fp32
 // (a pooled forward: the pooled values + their uint8 argmax).  fwd: x, W -> y; dgrad: dY, W -> dX; wgrad:
@@ -2658,8 +2656,119 @@ inline double conv_bytes(const ConvArgs& c, int mode, int esz) {
   return x * esz + dy + w * 4.0;
 }
 
+// ------------------------------------------------------------------ host dispatch
+// The profiler category of a conv GEMM: conv_fwd / conv_dgrad / conv_wgrad, "_lp" in the 16-bit modes
+const char* conv_cat(int mode, bool lp) {
+  static const char* const cat[2][3] = {{"conv_fwd", "conv_dgrad", "conv_wgrad"},
+                                        {"conv_fwd_lp", "conv_dgrad_lp", "conv_wgrad_lp"}};
+  return cat[lp][mode];
+}
+const char* conv_mode(int mode) { return mode == kFwd ? "fwd" : mode == kDgrad ? "dgrad" : "wgrad"; }
+
+// A call's geometry as ConvArgs; the caller adds its pointers and GEMM dims, run_conv_gemm the plan
+ConvArgs conv_args(int64_t N, int64_t H, int64_t W, int64_t Ci, int64_t Co, int64_t KH, int64_t KW, int64_t ph,
+                   int64_t pw, int64_t sh, int64_t sw, int64_t dil, int64_t Ho, int64_t Wo) {
+  ConvArgs c{};
+  c.N = (int)N; c.H = (int)H; c.W = (int)W; c.Ci = (int)Ci; c.Ho = (int)Ho; c.Wo = (int)Wo; c.Co = (int)Co;
+  c.KH = (int)KH; c.KW = (int)KW; c.ph = (int)ph; c.pw = (int)pw; c.sh = (int)sh; c.sw = (int)sw;
+  c.dil = (int)dil;
+  return c;
+}
+
+// w [Co][Ci][KH][KW] -> ws: the forward's Wt (to_dgrad 0) or the data gradient's Wd (1)
+void launch_weight_layout(const float* w, int64_t Co, int64_t Ci, int64_t KH, int64_t KW, int to_dgrad, float* ws,
+                          hipStream_t s) {
+  hipLaunchKernelGGL(weight_layout_kernel, dim3((unsigned)((Co * Ci * KH * KW + 255) / 256)), dim3(256), 0, s, w,
+                     (int)Co, (int)Ci, (int)KH, (int)KW, to_dgrad, ws);
+}
+
+// dWt in ws -> dw [Co][Ci][KH][KW] (accumulate: dw +=)
+void launch_weight_grad_layout(const float* ws, int64_t Co, int64_t Ci, int64_t KH, int64_t KW, float* dw,
+                               int accumulate, hipStream_t s) {
+  hipLaunchKernelGGL(weight_grad_layout_kernel, dim3((unsigned)((Co * Ci * KH * KW + 255) / 256)), dim3(256), 0, s, ws,
+                     (int)Co, (int)Ci, (int)KH, (int)KW, dw, accumulate);
+}
+
+// A forward's 16-bit sources when they qualify (s16_ok): x's copy goes to the caller's x16 where given (ready: it
+// already holds the producer's copy) and is reported in *x16_written, Wt's lives in scratch
+int fwd_sources16(ConvArgs& c, int prec, void* x16, bool x16_ready, int* x16_written, hipStream_t s) {
+  if (!s16_ok(prec, c.Ci, c.Co, {c.x, c.wmat, x16})) return SRK_OK;
+  const float* src[2] = {c.x, c.wmat};
+  const int64_t n[2] = {(int64_t)c.N * c.H * c.W * c.Ci, c.K * c.Nn};
+  unsigned short* d16[2] = {static_cast<unsigned short*>(x16), nullptr};   // x16: the caller keeps x's copy
+  const bool ready[2] = {x16_ready, false};
+  if (int rc = to16_all(prec, src, n, 2, d16, s, ready)) return rc;
+  c.a16 = d16[0];
+  c.b16 = d16[1];
+  if (x16 && x16_written) *x16_written = 1;
+  return SRK_OK;
+}
+
+// The split-K plan of an implicit GEMM on tm x tn tiles with bk-deep k-tiles; returns the split count
+int plan_split(ConvArgs& c, int64_t tm, int64_t tn, int bk, int splits0) {
+  c.kchunk = splits0 > 1 ? ((c.K + splits0 - 1) / splits0 + bk - 1) / bk * bk : std::max<int64_t>(c.K, 1);
+  const int splits = splits0 > 1 ? (int)((c.K + c.kchunk - 1) / c.kchunk) : 1;
+  c.tiles_m = (int)tm;
+  c.tiles_n = (int)tn;
+  c.tiles = (int)(tm * tn);
+  c.nblk = c.tiles * splits;
+  return splits;
+}
+
+// The slabs of a split and, for a weight gradient on fp32 sources, the bias-sum partials (the 16-bit-source
+// path keeps the column-sum kernel: fp32 dY)
 template <int MODE>
-int try_conv_ring(ConvArgs& c, hipStream_t s, const char* name, float* final_out, float** partial_out, int* splits_out) {
+int split_scratch(ConvArgs& c, int splits) {
+  c.partial = nullptr;
+  if (splits > 1) {
+    if (int rc = conv_scratch((size_t)splits * c.M * c.Nn, &c.partial)) return rc;
+  }
+  c.colsum_part = nullptr;
+  if (MODE == kWgrad && c.db && !c.a16) {
+    if (int rc = conv_scratch((size_t)splits * c.Nn, &c.colsum_part, g_csb)) return rc;
+  }
+  return SRK_OK;
+}
+
+// The gathers' divisors: pixel grid, channels of the gathered operand, KW, strides
+template <int MODE>
+void fill_divisors(ConvArgs& c) {
+  c.fd_w = FastDiv((unsigned)(MODE == kDgrad ? c.W : c.Wo));
+  c.fd_h = FastDiv((unsigned)(MODE == kDgrad ? c.H : c.Ho));
+  c.fd_c = FastDiv((unsigned)(MODE == kDgrad ? c.Co : c.Ci));
+  c.fd_kw = FastDiv((unsigned)c.KW);
+  c.fd_sh = FastDiv((unsigned)c.sh);
+  c.fd_sw = FastDiv((unsigned)c.sw);
+}
+
+// After the GEMM launch (c: the call, k: what the kernel got): the slab reduction (+ bias) of a split — a pooled
+// forward has no pooled epilogue across split-K slabs: dense, then pool — and the bias sums of a weight gradient
+template <int MODE>
+int conv_gemm_finish(const ConvArgs& c, const ConvArgs& k, int splits, hipStream_t s) {
+  if (splits > 1) {
+    const bool pool = MODE == kFwd && c.pool_w;
+    float* dense = c.out;
+    if (pool) {
+      if (int rc = conv_scratch((size_t)c.M * c.Nn, &dense, g_csd)) return rc;
+    }
+    launch_splitk_sum(k.partial, splits, c.M * c.Nn, c.Nn, MODE == kFwd ? c.bias : nullptr, dense, s);
+    if (pool) {
+      const int64_t rows = c.M / c.pool_w;
+      hipLaunchKernelGGL(maxpool_arg_kernel, dim3((unsigned)((rows * c.Nn + 255) / 256)), dim3(256), 0, s, dense,
+                         rows, (int)c.Nn, c.pool_w, c.out, c.pool_arg);
+    }
+  }
+  if (k.colsum_part)
+    hipLaunchKernelGGL(colsum_splits_kernel, dim3((unsigned)((c.Nn + 255) / 256)), dim3(256), 0, s, k.colsum_part,
+                       splits, c.Nn, c.db);
+  SRK_CHECK_HIP(hipGetLastError());
+  return SRK_OK;
+}
+
+// The ring conv when the shape qualifies (fp32 operands, option conv_ring, channel-aligned, stride 1
+// for the data gradient, 32-bit byte offsets); returns 1, with c untouched, if it did not run.
+template <int MODE>
+int try_conv_ring(ConvArgs& c, hipStream_t s, int* splits_out) {
   const int prec = matmul_prec();
   const bool lp = prec != kPrecF32;
   // fp32 operands (option bits 0..2), or the 16-bit operand copies of the S16 path (bits 4..6)
@@ -2697,30 +2806,14 @@ int try_conv_ring(ConvArgs& c, hipStream_t s, const char* name, float* final_out
     };
     if (t_of(1) <= t_of(splits0)) splits0 = 1;
   }
-  c.kchunk = splits0 > 1 ? ((c.K + splits0 - 1) / splits0 + RBK - 1) / RBK * RBK : std::max<int64_t>(c.K, 1);
-  const int splits = splits0 > 1 ? (int)((c.K + c.kchunk - 1) / c.kchunk) : 1;
-  c.tiles_m = (int)tm;
-  c.tiles_n = (int)tn;
-  c.tiles = (int)(tm * tn);
-  c.nblk = c.tiles * splits;
+  const int splits = plan_split(c, tm, tn, RBK, splits0);
   c.group_m = std::max(1, (int)std::lround(std::sqrt(32.0 * BN / 256.0)));
-  c.partial = nullptr;
-  if (splits > 1) {
-    if (int rc = conv_scratch((size_t)splits * c.M * c.Nn, &c.partial)) return rc;
-  }
-  c.colsum_part = nullptr;
-  if (MODE == kWgrad && c.db && !lp) {   // the 16-bit path keeps the column-sum kernel (fp32 dY)
-    if (int rc = conv_scratch((size_t)splits * c.Nn, &c.colsum_part, g_csb)) return rc;
-  }
-  c.fd_w = FastDiv((unsigned)(MODE == kDgrad ? c.W : c.Wo));
-  c.fd_h = FastDiv((unsigned)(MODE == kDgrad ? c.H : c.Ho));
-  c.fd_c = FastDiv((unsigned)chans);
-  c.fd_kw = FastDiv((unsigned)c.KW);
-  ProfScope prof(lp ? (MODE == kFwd ? "conv_fwd_lp" : MODE == kDgrad ? "conv_dgrad_lp" : "conv_wgrad_lp") : name, s,
-                 2.0 * (double)c.M * (double)c.Nn * (double)c.K);
+  if (int rc = split_scratch<MODE>(c, splits)) return rc;
+  fill_divisors<MODE>(c);
+  ProfScope prof(conv_cat(MODE, lp), s, 2.0 * (double)c.M * (double)c.Nn * (double)c.K);
   prof.bytes(conv_bytes(c, MODE, lp ? 2 : 4));
-  prof.detail("conv_ring%s_kernel<%s,256x%d%s%s> %lldx%lldx%lld s%d", lp ? "16" : "",
-              MODE == kFwd ? "fwd" : MODE == kDgrad ? "dgrad" : "wgrad", BN, (MODE == kFwd && c.pool_w) ? ",pool" : "",
+  prof.detail("conv_ring%s_kernel<%s,256x%d%s%s> %lldx%lldx%lld s%d", lp ? "16" : "", conv_mode(MODE), BN,
+              (MODE == kFwd && c.pool_w) ? ",pool" : "",
               lp && ((g_opt_conv_ring_qs >> (BN == 128 ? 1 : 2)) & 1) ? ",qs2" : "",
               (long long)c.M, (long long)c.Nn, (long long)c.K, splits);
   const dim3 grid((unsigned)c.nblk), block(512);
@@ -2742,58 +2835,28 @@ int try_conv_ring(ConvArgs& c, hipStream_t s, const char* name, float* final_out
 #undef SRK_R16
   }
   SRK_CHECK_HIP(hipGetLastError());
-  *partial_out = c.partial;
   *splits_out = splits;
-  (void)final_out;
   return 0;
 }
 
+// The implicit GEMM on the conv_gemm_kernel tiles (any shape), epilogue included: this path's profiler record
+// times the kernel together with its slab reduction, pooling and bias sums (the ring path's: the kernel alone)
 template <int MODE>
-int run_conv_gemm(ConvArgs c, hipStream_t s, const char* name) {
-  {
-    ConvArgs r = c;
-    float* partial = nullptr;
-    int splits = 1;
-    const int rc = try_conv_ring<MODE>(r, s, name, c.out, &partial, &splits);
-    if (rc == 0) {
-      if (splits > 1) {   // slab reduction (+ bias), then the pooled output / bias sums as below
-        const bool pool = MODE == kFwd && c.pool_w;
-        float* dense = c.out;
-        if (pool && (rc == 0)) {
-          if (int e = conv_scratch((size_t)c.M * c.Nn, &dense, g_csd)) return e;
-        }
-        const int64_t n = c.M * c.Nn;
-        launch_splitk_sum(partial, splits, n, c.Nn, MODE == kFwd ? c.bias : nullptr, dense, s);
-        if (pool) {
-          const int64_t rows = c.M / c.pool_w;
-          hipLaunchKernelGGL(maxpool_arg_kernel, dim3((unsigned)((rows * c.Nn + 255) / 256)), dim3(256), 0, s, dense,
-                             rows, (int)c.Nn, c.pool_w, c.out, c.pool_arg);
-        }
-        SRK_CHECK_HIP(hipGetLastError());
-      }
-      if (r.colsum_part) {
-        hipLaunchKernelGGL(colsum_splits_kernel, dim3((unsigned)((c.Nn + 255) / 256)), dim3(256), 0, s, r.colsum_part,
-                           splits, c.Nn, c.db);
-        SRK_CHECK_HIP(hipGetLastError());
-      }
-      return SRK_OK;
-    }
-    if (rc != 1) return rc;
-  }
+int conv_gemm_tiles(const ConvArgs& call, hipStream_t s) {
+  ConvArgs c = call;   // the kernel's copy: + the split plan, scratch and divisors
   const int prec = matmul_prec();
   const int BK = prec == kPrecF32 ? 32 : 64;   // 16-bit: 64-deep k-tiles (4 MFMA k-steps per barrier)
+  const int chans = MODE == kDgrad ? c.Co : c.Ci;
+  const bool vecb = c.Nn % 4 == 0;
+  const bool vec = (chans % 4 == 0) && vecb;
   // tile: 128 x 128 unless the GEMM is narrow (N <= 64: 128 x 64) or small (64 x 64); srk option
   // conv_tile = 256: 256 x BN tiles of 8 waves on tall GEMMs with vector gathers
   int BM = 128, BN = c.Nn <= 64 ? 64 : 128, NW = 4;
   if (((c.M + 127) / 128) * ((c.Nn + BN - 1) / BN) < 64 && c.K < 2048) { BM = 64; BN = 64; }
-  {
-    const int chans_ = MODE == kDgrad ? c.Co : c.Ci;
-    const bool vec_ = chans_ % 4 == 0 && c.Nn % 4 == 0;
-    if (g_opt_conv_tile == 256 && prec == kPrecF32 && BM == 128 && vec_ &&
-        ((c.M + 255) / 256) * ((c.Nn + BN - 1) / BN) >= kCUs) {
-      BM = 256;
-      NW = 8;
-    }
+  if (g_opt_conv_tile == 256 && prec == kPrecF32 && BM == 128 && vec &&
+      ((c.M + 255) / 256) * ((c.Nn + BN - 1) / BN) >= kCUs) {
+    BM = 256;
+    NW = 8;
   }
   const int64_t tm = (c.M + BM - 1) / BM, tn = (c.Nn + BN - 1) / BN;
   SRK_REQUIRE(tm * tn <= (INT32_MAX >> 9), SRK_ERR_INVALID, "conv: grid too large");
@@ -2802,41 +2865,12 @@ int run_conv_gemm(ConvArgs c, hipStream_t s, const char* name) {
   const int64_t slots = (int64_t)kCUs * std::min(8, (160 * 1024) / lds);
   // weight-gradient GEMMs reduce over every pixel (K up to millions) onto a few hundred tiles:
   // allow deep splits there (deterministic slab reduction)
-  const int splits0 = choose_splits(tm * tn, c.K, BK, slots, MODE == kWgrad ? 256 : 16);
-  c.kchunk = splits0 > 1 ? ((c.K + splits0 - 1) / splits0 + BK - 1) / BK * BK : std::max<int64_t>(c.K, 1);
-  const int splits = splits0 > 1 ? (int)((c.K + c.kchunk - 1) / c.kchunk) : 1;
-  c.tiles_m = (int)tm;
-  c.tiles_n = (int)tn;
-  c.tiles = (int)(tm * tn);
-  c.nblk = c.tiles * splits;
+  const int splits = plan_split(c, tm, tn, BK, choose_splits(tm * tn, c.K, BK, slots, MODE == kWgrad ? 256 : 16));
   c.group_m = 8;
-  c.partial = nullptr;
-  float* final_out = c.out;
-  float* pooled_out = nullptr;
-  int pool_w = 0;
-  if (splits > 1) {
-    if (int rc = conv_scratch((size_t)splits * c.M * c.Nn, &c.partial)) return rc;
-    if (MODE == kFwd && c.pool_w) {   // no pooled epilogue across split-K slabs: dense, then pool
-      pooled_out = c.out;
-      if (int rc = conv_scratch((size_t)c.M * c.Nn, &final_out, g_csd)) return rc;
-      pool_w = c.pool_w;
-      c.pool_w = 0;
-    }
-  }
-  c.colsum_part = nullptr;
-  if (MODE == kWgrad && c.db && !c.a16) {
-    if (int rc = conv_scratch((size_t)splits * c.Nn, &c.colsum_part, g_csb)) return rc;
-  }
-  const int chans = MODE == kDgrad ? c.Co : c.Ci;
+  if (splits > 1) c.pool_w = 0;   // a split pooled forward: the kernel fills slabs, conv_gemm_finish pools
+  if (int rc = split_scratch<MODE>(c, splits)) return rc;
   SRK_REQUIRE(c.M < INT32_MAX && c.K < INT32_MAX, SRK_ERR_INVALID, "conv: implicit-GEMM extent >= 2^31");
-  c.fd_w = FastDiv((unsigned)(MODE == kDgrad ? c.W : c.Wo));
-  c.fd_h = FastDiv((unsigned)(MODE == kDgrad ? c.H : c.Ho));
-  c.fd_c = FastDiv((unsigned)chans);
-  c.fd_kw = FastDiv((unsigned)c.KW);
-  c.fd_sh = FastDiv((unsigned)c.sh);
-  c.fd_sw = FastDiv((unsigned)c.sw);
-  const bool vecb = c.Nn % 4 == 0;
-  const bool vec = (chans % 4 == 0) && vecb;
+  fill_divisors<MODE>(c);
   {
     // fast16 gathers (ConvArgs::fast16): one tap per K-tile, 32-bit buffer offsets
     const double ael = MODE == kDgrad ? (double)c.N * c.Ho * c.Wo * c.Co : (double)c.N * c.H * c.W * c.Ci;
@@ -2848,11 +2882,10 @@ int run_conv_gemm(ConvArgs c, hipStream_t s, const char* name) {
               "conv: 16-bit sources need 8-aligned channels");
   SRK_REQUIRE(!c.dy_arg || (MODE != kFwd && !c.a16 && vec && vecb && c.sh == 1 && c.sw == 1 && c.Wo % 4 == 0),
               SRK_ERR_INTERNAL, "conv: unpooling gathers need fp32 sources, 4-aligned channels and Wo % 4 == 0");
-  ProfScope prof(prec == kPrecF32 ? name : (MODE == kFwd ? "conv_fwd_lp" : MODE == kDgrad ? "conv_dgrad_lp" : "conv_wgrad_lp"),
-                 s, 2.0 * (double)c.M * (double)c.Nn * (double)c.K);
+  ProfScope prof(conv_cat(MODE, prec != kPrecF32), s, 2.0 * (double)c.M * (double)c.Nn * (double)c.K);
   prof.bytes(conv_bytes(c, MODE, c.a16 ? 2 : 4));
-  prof.detail("conv_gemm_kernel<%s,%dx%d%s%s%s> %lldx%lldx%lld s%d", MODE == kFwd ? "fwd" : MODE == kDgrad ? "dgrad" : "wgrad",
-              BM, BN, NW == 8 ? ",8w" : "", c.a16 ? ",s16" : c.dy_arg ? ",unpool" : (MODE == kFwd && c.pool_w) ? ",pool" : "",
+  prof.detail("conv_gemm_kernel<%s,%dx%d%s%s%s> %lldx%lldx%lld s%d", conv_mode(MODE), BM, BN, NW == 8 ? ",8w" : "",
+              c.a16 ? ",s16" : c.dy_arg ? ",unpool" : (MODE == kFwd && c.pool_w) ? ",pool" : "",
               c.fast16 ? ",fast" : "", (long long)c.M, (long long)c.Nn, (long long)c.K, splits);
   const dim3 grid((unsigned)c.nblk);
   if (BM == 64) launch_conv<MODE, 64, 64>(c, grid, s, vec, vecb, prec);
@@ -2861,22 +2894,101 @@ int run_conv_gemm(ConvArgs c, hipStream_t s, const char* name) {
   else if (BN == 64) launch_conv<MODE, 128, 64>(c, grid, s, vec, vecb, prec);
   else launch_conv<MODE, 128, 128>(c, grid, s, vec, vecb, prec);
   SRK_CHECK_HIP(hipGetLastError());
-  if (splits > 1) {
-    const int64_t n = c.M * c.Nn;
-    launch_splitk_sum(c.partial, splits, n, c.Nn, MODE == kFwd ? c.bias : nullptr, final_out, s);
-    SRK_CHECK_HIP(hipGetLastError());
-    if (pooled_out) {
-      const int64_t rows = c.M / pool_w;
-      hipLaunchKernelGGL(maxpool_arg_kernel, dim3((unsigned)((rows * c.Nn + 255) / 256)), dim3(256), 0, s, final_out,
-                         rows, (int)c.Nn, pool_w, pooled_out, c.pool_arg);
-      SRK_CHECK_HIP(hipGetLastError());
-    }
+  return conv_gemm_finish<MODE>(call, c, splits, s);   // while prof lives
+}
+
+// The implicit GEMM of mode MODE: the ring kernels where they qualify, else the tile kernels
+template <int MODE>
+int run_conv_gemm(const ConvArgs& c, hipStream_t s) {
+  ConvArgs k = c;   // the ring kernel's copy
+  int splits = 1;
+  const int rc = try_conv_ring<MODE>(k, s, &splits);
+  if (rc == 1) return conv_gemm_tiles<MODE>(c, s);
+  return rc ? rc : conv_gemm_finish<MODE>(c, k, splits, s);
+}
+
+// fbanks_cnn conv2, Conv2d(64, 128, (1, 7), padding (0, 3)) over W = 40 (then MaxPool2d((1, 4))): the one geometry
+// the row-staged kernels are instantiated for, R image rows per tile.  Each kernel indexes with 32-bit offsets, so
+// each has its own limit on the image rows N * H.
+struct Conv2 {
+  static constexpr int KW = 7, PW = 3, W = 40, Ci = 64, Co = 128, R = 8;
+  static constexpr int64_t kRows16Fwd = (1LL << 30) / (W * Ci);      // conv_row16_pool: 16-bit x element offsets
+  static constexpr int64_t kRows16Bwd = (1LL << 30) / (W * Co);      // conv_row16_dgrad / _wgrad: 16-bit dY offsets
+  static constexpr int64_t kRows32Dgrad = (1LL << 29) / (W * Co);    // conv_row32_dgrad: fp32 dY offsets
+  static constexpr int64_t kRows32 = (1LL << 31) / (W * Ci * 4);     // conv_row32_pool / _wgrad: x byte offsets
+  static bool is(const ConvArgs& c, int64_t max_rows) {   // max_rows: the row limit of the kernel to be launched
+    return c.KH == 1 && c.KW == KW && c.ph == 0 && c.pw == PW && c.sh == 1 && c.sw == 1 && c.dil == 1 && c.W == W &&
+           c.Ci == Ci && c.Co == Co && (int64_t)c.N * c.H < max_rows;
   }
-  if (c.colsum_part) {
-    hipLaunchKernelGGL(colsum_splits_kernel, dim3((unsigned)((c.Nn + 255) / 256)), dim3(256), 0, s, c.colsum_part,
-                       splits, c.Nn, c.db);
-    SRK_CHECK_HIP(hipGetLastError());
+};
+// the row kernels' <KW, PW, WD, channels in, channels out, R>: forward / weight gradient, and data gradient
+#define SRK_C2 srk::Conv2::KW, srk::Conv2::PW, srk::Conv2::W, srk::Conv2::Ci, srk::Conv2::Co, srk::Conv2::R
+#define SRK_C2_DG srk::Conv2::KW, srk::Conv2::PW, srk::Conv2::W, srk::Conv2::Co, srk::Conv2::Ci, srk::Conv2::R
+
+// The row kernels' grid: groups of R image rows, dealt to G persistent workgroups
+struct RowGrid {
+  int64_t rows, groups, G;
+  explicit RowGrid(int64_t r) : rows(r), groups((r + Conv2::R - 1) / Conv2::R), G(std::min<int64_t>(groups, kCUs)) {}
+  // a row kernel's arguments with rows / groups set (under the kernel's row limit both fit an int)
+  template <class Args>
+  Args args() const {
+    Args a{};
+    a.rows = (int)rows;
+    a.groups = (int)groups;
+    return a;
   }
+};
+
+// conv_row16_pool_kernel: precision x waves per workgroup (option conv_row16 = 2: 4)
+void launch_row16_pool(int prec, const RowArgs& ra, const RowGrid& g, hipStream_t s) {
+  const bool w4 = g_opt_conv_row16 == 2;
+  const dim3 grid((unsigned)g.G), block(w4 ? 256 : 512);
+  if (prec == kPrecBF16) {
+    if (w4) hipLaunchKernelGGL((conv_row16_pool_kernel<1, SRK_C2, 4>), grid, block, 0, s, ra);
+    else hipLaunchKernelGGL((conv_row16_pool_kernel<1, SRK_C2, 8>), grid, block, 0, s, ra);
+  } else {
+    if (w4) hipLaunchKernelGGL((conv_row16_pool_kernel<2, SRK_C2, 4>), grid, block, 0, s, ra);
+    else hipLaunchKernelGGL((conv_row16_pool_kernel<2, SRK_C2, 8>), grid, block, 0, s, ra);
+  }
+}
+
+// conv_row16_dgrad_kernel: precision x BAL (option conv_row16_dgrad = 2), POOLED: ra.dyp / argp instead of ra.dy16
+template <bool POOLED>
+void launch_row16_dgrad(int prec, const RowDgArgs& ra, const RowGrid& g, hipStream_t s) {
+  const dim3 grid((unsigned)g.G), block(256);
+  const bool bal = g_opt_conv_row16_dgrad == 2;
+#define SRK_DG(LP_, BAL_) \
+  hipLaunchKernelGGL((conv_row16_dgrad_kernel<LP_, SRK_C2_DG, BAL_, POOLED>), grid, block, 0, s, ra)
+  if (prec == kPrecBF16 && bal) SRK_DG(1, true);
+  else if (prec == kPrecBF16) SRK_DG(1, false);
+  else if (bal) SRK_DG(2, true);
+  else SRK_DG(2, false);
+#undef SRK_DG
+}
+
+void launch_row16_wgrad(int prec, const Row16WgArgs& wa, const RowGrid& g, hipStream_t s) {
+  const dim3 grid((unsigned)g.G), block(512);
+  if (prec == kPrecBF16) hipLaunchKernelGGL((conv_row16_wgrad_kernel<1, SRK_C2>), grid, block, 0, s, wa);
+  else hipLaunchKernelGGL((conv_row16_wgrad_kernel<2, SRK_C2>), grid, block, 0, s, wa);
+}
+
+// The row-staged weight gradient of conv2: launch(slab, bpart) runs the kernel, one dWt slab (and, with db, one
+// row of bias sums) per workgroup; then the slabs reduced in order into ws, the bias sums, and dWt -> dw
+template <class Launch>
+int row_wgrad(const RowGrid& g, float* ws, float* dw, float* db, int dw_accumulate, hipStream_t s, Launch launch) {
+  const int64_t nslab = Conv2::KW * Conv2::Ci * Conv2::Co;
+  float* slab = nullptr;
+  float* bpart = nullptr;
+  if (int rc = conv_scratch((size_t)(g.G * nslab), &slab)) return rc;
+  if (db)
+    if (int rc = conv_scratch((size_t)(g.G * Conv2::Co), &bpart, g_csb)) return rc;
+  launch(slab, bpart);
+  launch_splitk_sum(slab, (int)g.G, nslab, Conv2::Co, nullptr, ws, s);
+  if (db)
+    hipLaunchKernelGGL(colsum_blocks_kernel, dim3((unsigned)((Conv2::Co + 63) / 64)), dim3(64 * kCsWaves), 0, s, bpart,
+                       (int)g.G, Conv2::Co, db);
+  launch_weight_grad_layout(ws, Conv2::Co, Conv2::Ci, 1, Conv2::KW, dw, dw_accumulate, s);
+  SRK_CHECK_HIP(hipGetLastError());
   return SRK_OK;
 }
 
@@ -2887,73 +2999,42 @@ int run_conv_gemm(ConvArgs c, hipStream_t s, const char* name) {
 // bias sums, colsum8 / unpool16) is never made.  x's 16-bit copy is the forward's when it kept one.
 int conv2_bwd16_pooled(const float* x, int64_t N, int64_t H, const float* w, const float* dyp, const uint8_t* arg,
                        float* dx, float* dw, float* db, float* ws, const void* x16, hipStream_t s) {
-  constexpr int64_t W = 40, Ci = 64, Co = 128, KH = 1, KW = 7;
+  constexpr int64_t W = Conv2::W, Ci = Conv2::Ci, Co = Conv2::Co, KW = Conv2::KW;
   const int prec = matmul_prec();
-  const int64_t nw = Co * Ci * KH * KW, rows = N * H, groups = (rows + 7) / 8;
-  int rc;
-  if (dx)
-    hipLaunchKernelGGL(weight_layout_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, w, (int)Co, (int)Ci,
-                       (int)KH, (int)KW, 1, ws);
+  const RowGrid g(N * H);
+  const int64_t nw = Co * Ci * KW, px = N * H * W;
+  if (dx) launch_weight_layout(w, Co, Ci, 1, KW, 1, ws, s);
   unsigned short* d16[2] = {static_cast<unsigned short*>(const_cast<void*>(x16)), nullptr};   // x, Wd
   {
     const float* src[2] = {x, ws};
-    const int64_t n[2] = {rows * W * Ci, nw};
+    const int64_t n[2] = {px * Ci, nw};
     const bool ready[2] = {x16 != nullptr, false};
-    if ((rc = to16_all(prec, src, n, dx ? 2 : 1, d16, s, ready))) return rc;
+    if (int rc = to16_all(prec, src, n, dx ? 2 : 1, d16, s, ready)) return rc;
   }
   if (dx) {
-    RowDgArgs ra{};
+    RowDgArgs ra = g.args<RowDgArgs>();
     ra.wd16 = d16[1];
     ra.dx = dx;
-    ra.rows = (int)rows;
-    ra.groups = (int)groups;
     ra.dyp = dyp;
     ra.argp = arg;
-    ProfScope prof("conv_dgrad_lp", s, 2.0 * (double)(rows * W) * (double)Ci * (double)(KW * Co));
-    prof.detail("conv_row16_dgrad_kernel<unpool> %lldx%lldx%lld", (long long)(rows * W), (long long)Ci, (long long)(KW * Co));
-    prof.bytes(5.0 / 4.0 * (double)(rows * W) * Co + 2.0 * (double)(KW * Co) * Ci + 4.0 * (double)(rows * W) * Ci);
-    const dim3 grid((unsigned)std::min<int64_t>(groups, kCUs)), block(256);
-    const bool bal = g_opt_conv_row16_dgrad == 2;
-    if (prec == kPrecBF16 && bal)
-      hipLaunchKernelGGL((conv_row16_dgrad_kernel<1, 7, 3, 40, 128, 64, 8, true, true>), grid, block, 0, s, ra);
-    else if (prec == kPrecBF16)
-      hipLaunchKernelGGL((conv_row16_dgrad_kernel<1, 7, 3, 40, 128, 64, 8, false, true>), grid, block, 0, s, ra);
-    else if (bal)
-      hipLaunchKernelGGL((conv_row16_dgrad_kernel<2, 7, 3, 40, 128, 64, 8, true, true>), grid, block, 0, s, ra);
-    else
-      hipLaunchKernelGGL((conv_row16_dgrad_kernel<2, 7, 3, 40, 128, 64, 8, false, true>), grid, block, 0, s, ra);
+    ProfScope prof("conv_dgrad_lp", s, 2.0 * (double)px * (double)Ci * (double)(KW * Co));
+    prof.detail("conv_row16_dgrad_kernel<unpool> %lldx%lldx%lld", (long long)px, (long long)Ci, (long long)(KW * Co));
+    prof.bytes(5.0 / 4.0 * (double)px * Co + 2.0 * (double)(KW * Co) * Ci + 4.0 * (double)px * Ci);
+    launch_row16_dgrad<true>(prec, ra, g, s);
     SRK_CHECK_HIP(hipGetLastError());
   }
-  const int64_t G = std::min<int64_t>(groups, kCUs), nslab = KW * Ci * Co;
-  float* slab = nullptr;
-  float* bpart = nullptr;
-  if ((rc = conv_scratch((size_t)(G * nslab), &slab))) return rc;
-  if (db && (rc = conv_scratch((size_t)(G * Co), &bpart, g_csb))) return rc;
-  Row16WgArgs wa{};
-  wa.x16 = d16[0];
-  wa.dy = dyp;
-  wa.arg = arg;
-  wa.slab = slab;
-  wa.bpart = bpart;
-  wa.rows = (int)rows;
-  wa.groups = (int)groups;
-  {
-    ProfScope prof("conv_wgrad_lp", s, 2.0 * (double)(rows * W) * (double)(KW * Ci) * (double)Co);
-    prof.detail("conv_row16_wgrad_kernel<unpool> %lldx%lldx%lld", (long long)(KW * Ci), (long long)Co, (long long)(rows * W));
-    prof.bytes(2.0 * (double)(rows * W) * Ci + 5.0 / 4.0 * (double)(rows * W) * Co + 4.0 * (double)(G * nslab));
-    if (prec == kPrecBF16)
-      hipLaunchKernelGGL((conv_row16_wgrad_kernel<1, 7, 3, 40, 64, 128, 8>), dim3((unsigned)G), dim3(512), 0, s, wa);
-    else
-      hipLaunchKernelGGL((conv_row16_wgrad_kernel<2, 7, 3, 40, 64, 128, 8>), dim3((unsigned)G), dim3(512), 0, s, wa);
-  }
-  launch_splitk_sum(slab, (int)G, nslab, Co, nullptr, ws, s);
-  if (bpart)
-    hipLaunchKernelGGL(colsum_blocks_kernel, dim3((unsigned)((Co + 63) / 64)), dim3(64 * kCsWaves), 0, s, bpart, (int)G,
-                       (int)Co, db);
-  hipLaunchKernelGGL(weight_grad_layout_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, ws, (int)Co,
-                     (int)Ci, (int)KH, (int)KW, dw, 0);
-  SRK_CHECK_HIP(hipGetLastError());
-  return SRK_OK;
+  return row_wgrad(g, ws, dw, db, 0, s, [&](float* slab, float* bpart) {
+    Row16WgArgs wa = g.args<Row16WgArgs>();
+    wa.x16 = d16[0];
+    wa.dy = dyp;
+    wa.arg = arg;
+    wa.slab = slab;
+    wa.bpart = bpart;
+    ProfScope prof("conv_wgrad_lp", s, 2.0 * (double)px * (double)(KW * Ci) * (double)Co);
+    prof.detail("conv_row16_wgrad_kernel<unpool> %lldx%lldx%lld", (long long)(KW * Ci), (long long)Co, (long long)px);
+    prof.bytes(2.0 * (double)px * Ci + 5.0 / 4.0 * (double)px * Co + 4.0 * (double)(g.G * KW * Ci * Co));
+    launch_row16_wgrad(prec, wa, g, s);
+  });
 }
 
 int check(int64_t N, int64_t H, int64_t W, int64_t Ci, int64_t Co, int64_t KH, int64_t KW, int64_t ph, int64_t pw,
@@ -2965,6 +3046,17 @@ int check(int64_t N, int64_t H, int64_t W, int64_t Ci, int64_t Co, int64_t KH, i
   SRK_REQUIRE(*Ho > 0 && *Wo > 0, SRK_ERR_INVALID, "conv: empty output");
   SRK_REQUIRE(N * H * W * Ci < ((int64_t)1 << 40) && N * (*Ho) * (*Wo) * Co < ((int64_t)1 << 40), SRK_ERR_INVALID,
               "conv: too large");
+  return SRK_OK;
+}
+
+// the geometry of the dilated 1-D entry points (srk_conv1d_nlc_dil_fwd / _bwd)
+int check_dil(int64_t N, int64_t L, int64_t Ci, int64_t Co, int64_t K, int64_t pad, int64_t dil) {
+  SRK_REQUIRE(dil >= 1, SRK_ERR_INVALID, "conv1d dilation: dil = %lld, must be >= 1", (long long)dil);
+  SRK_REQUIRE(N > 0 && L > 0 && Ci > 0 && Co > 0 && K > 0 && pad >= 0 && pad < (1 << 28) && dil < (1 << 20) && K < (1 << 20),
+              SRK_ERR_INVALID, "conv1d dilation: bad dims");
+  SRK_REQUIRE(L + 2 * pad - dil * (K - 1) >= 1, SRK_ERR_INVALID,
+              "conv1d dilation: empty output (L %lld + 2 pad %lld < receptive field %lld)", (long long)L, (long long)pad,
+              (long long)(dil * (K - 1) + 1));
   return SRK_OK;
 }
 
@@ -2994,13 +3086,8 @@ int conv_fwd(const float* x, int64_t N, int64_t H, int64_t W, int64_t Ci, const 
   if (int rc = srk::check(N, H, W, Ci, Co, KH, KW, ph, pw, sh, sw, &Ho, &Wo, dil)) return rc;
   SRK_REQUIRE(x && w && y && ws, SRK_ERR_INVALID, "conv fwd: null pointer");
   hipStream_t s = srk::as_stream(stream);
-  const int64_t nw = Co * Ci * KH * KW;
-  hipLaunchKernelGGL(srk::weight_layout_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, w, (int)Co,
-                     (int)Ci, (int)KH, (int)KW, 0, ws);
-  srk::ConvArgs c{};
-  c.N = (int)N; c.H = (int)H; c.W = (int)W; c.Ci = (int)Ci; c.Ho = (int)Ho; c.Wo = (int)Wo; c.Co = (int)Co;
-  c.KH = (int)KH; c.KW = (int)KW; c.ph = (int)ph; c.pw = (int)pw; c.sh = (int)sh; c.sw = (int)sw;
-  c.dil = (int)dil;
+  srk::launch_weight_layout(w, Co, Ci, KH, KW, 0, ws, s);
+  srk::ConvArgs c = srk::conv_args(N, H, W, Ci, Co, KH, KW, ph, pw, sh, sw, dil, Ho, Wo);
   c.x = x; c.wmat = ws; c.out = y; c.bias = bias;
   c.M = N * Ho * Wo; c.Nn = Co; c.K = KH * KW * Ci;
   // A full-width "valid" conv (model_fbanks_cnn.py:74, conv3 (1, 10) on width 10) is the plain GEMM
@@ -3008,40 +3095,27 @@ int conv_fwd(const float* x, int64_t N, int64_t H, int64_t W, int64_t Ci, const 
   // (x rows are already the GEMM rows: no gather, no split-K slabs of the implicit GEMM's tall 2-tile-wide grid)
   const bool full_width =
       KH == 1 && ph == 0 && pw == 0 && sh == 1 && KW == W && Wo == 1 && dil == 1 && srk::g_opt_conv_fw_gemm;
-  auto fw_gemm = [&](const unsigned short* a16, const unsigned short* b16, const char* cat) -> int {
+  auto fw_gemm = [&]() -> int {
     srk::GemmDesc g;
     g.M = N * H; g.N = Co; g.K = KW * Ci;
     g.A = x; g.lda = KW * Ci;
     g.B = ws; g.ldb = Co;
     g.C = y; g.ldc = Co;
     g.bias = bias; g.bias_mode = bias ? 1 : 0;
-    g.A16 = a16; g.B16 = b16;
-    srk::ProfScope prof(cat, s, 2.0 * (double)g.M * (double)g.N * (double)g.K);
+    g.A16 = c.a16; g.B16 = c.b16;
+    srk::ProfScope prof(srk::conv_cat(srk::kFwd, srk::matmul_prec() != srk::kPrecF32), s,
+                        2.0 * (double)g.M * (double)g.N * (double)g.K);
     prof.detail("conv_fwd_as_gemm %lldx%lldx%lld", (long long)g.M, (long long)g.N, (long long)g.K);
-    prof.bytes((a16 ? 2.0 : 4.0) * ((double)g.M * g.K + (double)g.K * g.N) + 4.0 * (double)g.M * g.N);
+    prof.bytes((c.a16 ? 2.0 : 4.0) * ((double)g.M * g.K + (double)g.K * g.N) + 4.0 * (double)g.M * g.N);
     return srk::gemm_f32(g, s);
   };
-  if (srk::g_opt_conv_fwd_fp32 && srk::matmul_prec() != srk::kPrecF32) {
-    // the faithful 16-bit mode: this forward on fp32 operands; a producer's 16-bit copy of x stays the
-    // backward's (its weight gradient runs 16-bit)
-    if (x16_ready && x16_written) *x16_written = 1;
-    srk::PrecScope fp32(srk::kPrecF32);
-    if (full_width) return fw_gemm(nullptr, nullptr, "conv_fwd");
-    return srk::run_conv_gemm<srk::kFwd>(c, s, "conv_fwd");
-  }
-  const int prec = srk::matmul_prec();
-  if (srk::s16_ok(prec, Ci, Co, {x, ws, x16})) {
-    const float* src[2] = {x, ws};
-    const int64_t n[2] = {N * H * W * Ci, nw};
-    unsigned short* d16[2] = {static_cast<unsigned short*>(x16), nullptr};   // x16: the caller keeps x's copy
-    const bool ready[2] = {x16_ready, false};
-    if (int rc = srk::to16_all(prec, src, n, 2, d16, s, ready)) return rc;
-    c.a16 = d16[0];
-    c.b16 = d16[1];
-    if (x16 && x16_written) *x16_written = 1;
-  }
-  if (full_width) return fw_gemm(c.a16, c.b16, prec == srk::kPrecF32 ? "conv_fwd" : "conv_fwd_lp");
-  return srk::run_conv_gemm<srk::kFwd>(c, s, "conv_fwd");
+  // the faithful 16-bit mode (option conv_fwd_fp32): this forward on fp32 operands (no 16-bit sources then); a
+  // producer's 16-bit copy of x stays the backward's (its weight gradient runs 16-bit)
+  const bool fwd32 = srk::g_opt_conv_fwd_fp32 && srk::matmul_prec() != srk::kPrecF32;
+  if (fwd32 && x16_ready) *x16_written = 1;
+  srk::PrecScope fp32(fwd32 ? srk::kPrecF32 : -1);
+  if (int rc = srk::fwd_sources16(c, srk::matmul_prec(), x16, x16_ready, x16_written, s)) return rc;
+  return full_width ? fw_gemm() : srk::run_conv_gemm<srk::kFwd>(c, s);
 }
 }  // namespace srk
 
@@ -3079,10 +3153,7 @@ int conv_bwd(const float* x, int64_t N, int64_t H, int64_t W, int64_t Ci, const 
   SRK_REQUIRE(x && w && (dy || dy16) && dw && ws, SRK_ERR_INVALID, "conv bwd: null pointer");
   hipStream_t s = srk::as_stream(stream);
   const int64_t nw = Co * Ci * KH * KW;
-  srk::ConvArgs c{};
-  c.N = (int)N; c.H = (int)H; c.W = (int)W; c.Ci = (int)Ci; c.Ho = (int)Ho; c.Wo = (int)Wo; c.Co = (int)Co;
-  c.KH = (int)KH; c.KW = (int)KW; c.ph = (int)ph; c.pw = (int)pw; c.sh = (int)sh; c.sw = (int)sw;
-  c.dil = (int)dil;
+  srk::ConvArgs c = srk::conv_args(N, H, W, Ci, Co, KH, KW, ph, pw, sh, sw, dil, Ho, Wo);
   c.x = x; c.dy = dy;
   c.dy_arg = dy_arg;
   int rc;
@@ -3094,9 +3165,7 @@ int conv_bwd(const float* x, int64_t N, int64_t H, int64_t W, int64_t Ci, const 
   SRK_REQUIRE(!dy16 || dy || (!dy_arg && !full_width && !db && srk::s16_ok(srk::matmul_prec(), Ci, Co, {x, ws, x16, dy16})),
               SRK_ERR_INTERNAL, "conv bwd: a 16-bit dY needs the 16-bit-source implicit GEMMs");
   const bool dgrad_implicit = dx && !full_width;
-  if (dgrad_implicit)
-    hipLaunchKernelGGL(srk::weight_layout_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, w, (int)Co,
-                       (int)Ci, (int)KH, (int)KW, 1, ws);
+  if (dgrad_implicit) srk::launch_weight_layout(w, Co, Ci, KH, KW, 1, ws, s);
   // 16-bit sources: x and dY serve both GEMMs, Wd the data gradient (one scratch allocation)
   unsigned short* d16[3] = {nullptr, nullptr, nullptr};   // x, dY, Wd
   const int prec = srk::matmul_prec();
@@ -3120,120 +3189,85 @@ int conv_bwd(const float* x, int64_t N, int64_t H, int64_t W, int64_t Ci, const 
       db_done = true;
     }
   }
+  // the fp32 row kernels of fbanks_cnn conv2 read the pooled gradient + argmax
+  const bool row32 = !d16[0] && prec == srk::kPrecF32 && srk::g_opt_conv_row32 && dy && dy_arg;
+  const srk::RowGrid rg(N * H);
   if (dx && full_width) {
     // A full-width "valid" conv (model_fbanks_cnn.py:74, conv3 1x10 on width 10): every input
     // column meets exactly one tap, so the data gradient is the plain GEMM
     //   dX[(n,h)][(kw,ci)] = dY[(n,h)][co] * Wt[(kw,ci)][co]^T
     // instead of an implicit GEMM whose k range is 90 % structurally-zero taps.
-    hipLaunchKernelGGL(srk::weight_layout_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, w, (int)Co,
-                       (int)Ci, (int)KH, (int)KW, 0, ws);
+    srk::launch_weight_layout(w, Co, Ci, KH, KW, 0, ws, s);
     srk::GemmDesc g;
     g.M = N * H; g.N = KW * Ci; g.K = Co;
     g.A = dy; g.lda = Co;
     g.B = ws; g.ldb = Co; g.tb = true;
     g.C = dx; g.ldc = KW * Ci;
-    srk::ProfScope prof(srk::matmul_prec() == srk::kPrecF32 ? "conv_dgrad" : "conv_dgrad_lp", s,
+    srk::ProfScope prof(srk::conv_cat(srk::kDgrad, prec != srk::kPrecF32), s,
                         2.0 * (double)g.M * (double)g.N * (double)g.K);
     prof.detail("conv_dgrad_as_gemm %lldx%lldx%lld", (long long)g.M, (long long)g.N, (long long)g.K);
     prof.bytes(4.0 * ((double)g.M * g.K + (double)g.K * g.N + (double)g.M * g.N));
     if ((rc = srk::gemm_f32(g, s))) return rc;
-  } else if (dgrad_implicit && d16[0] && dil == 1 && srk::g_opt_conv_row16_dgrad && KH == 1 && KW == 7 && ph == 0 &&
-             pw == 3 && sh == 1 && sw == 1 && W == 40 && Ci == 64 && Co == 128 && (N * H) < (1LL << 30) / (W * Co)) {
+  } else if (dgrad_implicit && d16[0] && srk::g_opt_conv_row16_dgrad && srk::Conv2::is(c, srk::Conv2::kRows16Bwd)) {
     // fbanks_cnn conv2's data gradient: the row-staged kernel (conv_row16_dgrad_kernel)
-    srk::RowDgArgs ra{};
+    srk::RowDgArgs ra = rg.args<srk::RowDgArgs>();
     ra.dy16 = d16[1];
     ra.wd16 = d16[2];
     ra.dx = dx;
-    ra.rows = (int)(N * H);
-    ra.groups = (int)((N * H + 7) / 8);
     srk::ProfScope prof("conv_dgrad_lp", s, 2.0 * (double)(N * H * W) * (double)Ci * (double)(KW * Co));
     prof.detail("conv_row16_dgrad_kernel %lldx%lldx%lld", (long long)(N * H * W), (long long)Ci, (long long)(KW * Co));
     prof.bytes(2.0 * (double)(N * H * W) * Co + 2.0 * (double)(KW * Co) * Ci + 4.0 * (double)(N * H * W) * Ci);
-    const dim3 grid((unsigned)std::min<int64_t>(ra.groups, srk::kCUs)), block(256);
-    const bool bal = srk::g_opt_conv_row16_dgrad == 2;
-    if (prec == srk::kPrecBF16 && bal)
-      hipLaunchKernelGGL((srk::conv_row16_dgrad_kernel<1, 7, 3, 40, 128, 64, 8, true>), grid, block, 0, s, ra);
-    else if (prec == srk::kPrecBF16)
-      hipLaunchKernelGGL((srk::conv_row16_dgrad_kernel<1, 7, 3, 40, 128, 64, 8>), grid, block, 0, s, ra);
-    else if (bal)
-      hipLaunchKernelGGL((srk::conv_row16_dgrad_kernel<2, 7, 3, 40, 128, 64, 8, true>), grid, block, 0, s, ra);
-    else
-      hipLaunchKernelGGL((srk::conv_row16_dgrad_kernel<2, 7, 3, 40, 128, 64, 8>), grid, block, 0, s, ra);
-  } else if (dgrad_implicit && !d16[0] && prec == srk::kPrecF32 && srk::g_opt_conv_row32 && KH == 1 && KW == 7 &&
-             ph == 0 && pw == 3 && sh == 1 && sw == 1 && W == 40 && Ci == 64 && Co == 128 && dy && dy_arg &&
-             (N * H) < (1LL << 29) / (W * Co)) {
+    srk::launch_row16_dgrad<false>(prec, ra, rg, s);
+  } else if (dgrad_implicit && row32 && srk::Conv2::is(c, srk::Conv2::kRows32Dgrad)) {
     // fbanks_cnn conv2's data gradient on fp32 operands (the pooled backward: the pooled gradient + argmax): the
     // row-staged kernel (conv_row32_dgrad_kernel; its dense-dY form spills at one wave per SIMD, not used)
-    srk::Row32DgArgs ra{};
+    srk::Row32DgArgs ra = rg.args<srk::Row32DgArgs>();
     ra.dy = dy;
     ra.arg = dy_arg;
     ra.wd = ws;
     ra.dx = dx;
-    ra.rows = (int)(N * H);
-    ra.groups = (int)((N * H + 7) / 8);
     srk::ProfScope prof("conv_dgrad", s, 2.0 * (double)(N * H * W) * (double)Ci * (double)(KW * Co));
     prof.detail("conv_row32_dgrad_kernel<unpool> %lldx%lldx%lld", (long long)(N * H * W), (long long)Ci,
                 (long long)(KW * Co));
     prof.bytes(5.0 / 4.0 * (double)(N * H * W) * Co + 4.0 * (double)(KW * Co) * Ci + 4.0 * (double)(N * H * W) * Ci);
-    const dim3 grid((unsigned)std::min<int64_t>(ra.groups, srk::kCUs)), block(256);
-    hipLaunchKernelGGL((srk::conv_row32_dgrad_kernel<7, 3, 40, 128, 64, 8, true>), grid, block, 0, s, ra);
+    hipLaunchKernelGGL((srk::conv_row32_dgrad_kernel<SRK_C2_DG, true>), dim3((unsigned)rg.G), dim3(256), 0, s, ra);
   } else if (dgrad_implicit) {
     srk::ConvArgs d = c;
     d.wmat = ws; d.out = dx;
     d.M = N * H * W; d.Nn = Ci; d.K = KH * KW * Co;
-    if (d16[0]) {
-      d.a16 = d16[1];
-      d.b16 = d16[2];
-    }
-    if ((rc = srk::run_conv_gemm<srk::kDgrad>(d, s, "conv_dgrad"))) return rc;
+    d.a16 = d16[1];   // null without 16-bit sources
+    d.b16 = d16[2];
+    if ((rc = srk::run_conv_gemm<srk::kDgrad>(d, s))) return rc;
   }
-  if (!d16[0] && prec == srk::kPrecF32 && srk::g_opt_conv_row32 && KH == 1 && KW == 7 && ph == 0 && pw == 3 &&
-      sh == 1 && sw == 1 && W == 40 && Ci == 64 && Co == 128 && dy && dy_arg && (N * H) < (1LL << 31) / (W * Ci * 4)) {
+  if (row32 && srk::Conv2::is(c, srk::Conv2::kRows32)) {
     // fbanks_cnn conv2's weight gradient on fp32 operands from the pooled gradient + argmax: the row-staged kernel
     // (conv_row32_wgrad_kernel), one slab per workgroup, reduced in order; the bias gradient from the same pass
-    const int64_t rows = N * H, groups = (rows + 7) / 8, G = std::min<int64_t>(groups, srk::kCUs);
-    const int64_t nslab = KW * Ci * Co;
-    float* slab = nullptr;
-    float* bpart = nullptr;
-    if ((rc = srk::conv_scratch((size_t)(G * nslab), &slab))) return rc;
-    if (db && (rc = srk::conv_scratch((size_t)(G * Co), &bpart, srk::g_csb))) return rc;
-    srk::Row32WgArgs ra{};
-    ra.x = x;
-    ra.dy = dy;
-    ra.arg = dy_arg;
-    ra.slab = slab;
-    ra.bpart = bpart;
-    ra.rows = (int)rows;
-    ra.groups = (int)groups;
-    {
+    return srk::row_wgrad(rg, ws, dw, db, dw_accumulate, s, [&](float* slab, float* bpart) {
+      srk::Row32WgArgs ra = rg.args<srk::Row32WgArgs>();
+      ra.x = x;
+      ra.dy = dy;
+      ra.arg = dy_arg;
+      ra.slab = slab;
+      ra.bpart = bpart;
       srk::ProfScope prof("conv_wgrad", s, 2.0 * (double)(N * H * W) * (double)(KW * Ci) * (double)Co);
       prof.detail("conv_row32_wgrad_kernel<unpool> %lldx%lldx%lld", (long long)(KW * Ci), (long long)Co,
                   (long long)(N * H * W));
-      prof.bytes(4.0 * (double)(N * H * W) * Ci + 5.0 / 4.0 * (double)(N * H * W) * Co + 4.0 * (double)(G * nslab));
-      hipLaunchKernelGGL((srk::conv_row32_wgrad_kernel<7, 3, 40, 64, 128, 8>), dim3((unsigned)G), dim3(512), 0, s, ra);
-    }
-    srk::launch_splitk_sum(slab, (int)G, nslab, Co, nullptr, ws, s);
-    if (db)
-      hipLaunchKernelGGL(srk::colsum_blocks_kernel, dim3((unsigned)((Co + 63) / 64)), dim3(64 * srk::kCsWaves), 0, s,
-                         bpart, (int)G, (int)Co, db);
-    hipLaunchKernelGGL(srk::weight_grad_layout_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, ws,
-                       (int)Co, (int)Ci, (int)KH, (int)KW, dw, dw_accumulate);
-  } else {
-    srk::ConvArgs g = c;
-    g.out = ws;   // dWt [(kh,kw,ci)][co], then re-laid out into dw
-    g.M = KH * KW * Ci; g.Nn = Co; g.K = N * Ho * Wo;
-    if (d16[0]) {
-      g.a16 = d16[0];
-      g.b16 = d16[1];
-    }
-    // the bias gradient = column sums of dY, fused into the weight-gradient kernel (fp32-source
-    // paths: the sums of the unrounded values); the 16-bit-source path keeps the column-sum kernel
-    g.db = srk::g_opt_conv_fused_db ? db : nullptr;
-    if ((rc = srk::run_conv_gemm<srk::kWgrad>(g, s, "conv_wgrad"))) return rc;
-    hipLaunchKernelGGL(srk::weight_grad_layout_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, ws,
-                       (int)Co, (int)Ci, (int)KH, (int)KW, dw, dw_accumulate);
-    if (db && !db_done && (!g.db || g.a16) && (rc = srk::colsum_f32(dy, N * Ho * Wo, Co, Co, db, 0.f, s))) return rc;
+      prof.bytes(4.0 * (double)(N * H * W) * Ci + 5.0 / 4.0 * (double)(N * H * W) * Co +
+                 4.0 * (double)(rg.G * KW * Ci * Co));
+      hipLaunchKernelGGL((srk::conv_row32_wgrad_kernel<SRK_C2>), dim3((unsigned)rg.G), dim3(512), 0, s, ra);
+    });
   }
+  srk::ConvArgs g = c;
+  g.out = ws;   // dWt [(kh,kw,ci)][co], then re-laid out into dw
+  g.M = KH * KW * Ci; g.Nn = Co; g.K = N * Ho * Wo;
+  g.a16 = d16[0];
+  g.b16 = d16[1];
+  // the bias gradient = column sums of dY, fused into the weight-gradient kernel (fp32-source
+  // paths: the sums of the unrounded values); the 16-bit-source path keeps the column-sum kernel
+  g.db = srk::g_opt_conv_fused_db ? db : nullptr;
+  if ((rc = srk::run_conv_gemm<srk::kWgrad>(g, s))) return rc;
+  srk::launch_weight_grad_layout(ws, Co, Ci, KH, KW, dw, dw_accumulate, s);
+  if (db && !db_done && (!g.db || g.a16) && (rc = srk::colsum_f32(dy, N * Ho * Wo, Co, Co, db, 0.f, s))) return rc;
   SRK_CHECK_HIP(hipGetLastError());
   return SRK_OK;
 }
@@ -3274,12 +3308,7 @@ int srk_conv1d_nlc_dil_fwd(const float* x, int64_t N, int64_t L, int64_t Ci, con
                            int64_t Co, int64_t K, int64_t pad, int64_t dil, float* y, float* ws, void* x16,
                            int* x16_written, void* stream) {
   SRK_API_BEGIN
-  SRK_REQUIRE(dil >= 1, SRK_ERR_INVALID, "conv1d dilation: dil = %lld, must be >= 1", (long long)dil);
-  SRK_REQUIRE(N > 0 && L > 0 && Ci > 0 && Co > 0 && K > 0 && pad >= 0 && pad < (1 << 28) && dil < (1 << 20) && K < (1 << 20),
-              SRK_ERR_INVALID, "conv1d dilation: bad dims");
-  SRK_REQUIRE(L + 2 * pad - dil * (K - 1) >= 1, SRK_ERR_INVALID,
-              "conv1d dilation: empty output (L %lld + 2 pad %lld < receptive field %lld)", (long long)L, (long long)pad,
-              (long long)(dil * (K - 1) + 1));
+  if (int rc = srk::check_dil(N, L, Ci, Co, K, pad, dil)) return rc;
   SRK_REQUIRE(x && w && y && ws, SRK_ERR_INVALID, "conv1d dilation fwd: null pointer");
   if (dil == 1)
     return srk_conv2d_nhwc_fwd16(x, N, 1, L, Ci, w, bias, Co, 1, K, 0, pad, 1, 1, y, ws, x16, x16_written, stream);
@@ -3291,12 +3320,7 @@ int srk_conv1d_nlc_dil_bwd(const float* x, int64_t N, int64_t L, int64_t Ci, con
                            int64_t pad, int64_t dil, const float* dy, const void* dy16, float* dx, float* dw,
                            float* db, float* ws, const void* x16, int dw_accumulate, void* stream) {
   SRK_API_BEGIN
-  SRK_REQUIRE(dil >= 1, SRK_ERR_INVALID, "conv1d dilation: dil = %lld, must be >= 1", (long long)dil);
-  SRK_REQUIRE(N > 0 && L > 0 && Ci > 0 && Co > 0 && K > 0 && pad >= 0 && pad < (1 << 28) && dil < (1 << 20) && K < (1 << 20),
-              SRK_ERR_INVALID, "conv1d dilation: bad dims");
-  SRK_REQUIRE(L + 2 * pad - dil * (K - 1) >= 1, SRK_ERR_INVALID,
-              "conv1d dilation: empty output (L %lld + 2 pad %lld < receptive field %lld)", (long long)L, (long long)pad,
-              (long long)(dil * (K - 1) + 1));
+  if (int rc = srk::check_dil(N, L, Ci, Co, K, pad, dil)) return rc;
   SRK_REQUIRE(x && w && dy && dw && ws, SRK_ERR_INVALID, "conv1d dilation bwd: null pointer");
   if (dil == 1)
     return srk_conv2d_nhwc_bwd16_acc(x, N, 1, L, Ci, w, Co, 1, K, 0, pad, 1, 1, dy, dy16, dx, dw, db, ws, x16,
@@ -3325,75 +3349,48 @@ int srk_conv2d_nhwc_fwd_pool(const float* x, int64_t N, int64_t H, int64_t W, in
   SRK_REQUIRE(pool_w == 4 && Wo % pool_w == 0, SRK_ERR_INVALID,
               "conv fwd_pool: the fused pooling needs a (1, 4) window that divides the output width");
   hipStream_t s = srk::as_stream(stream);
-  const int64_t nw = Co * Ci * KH * KW;
-  hipLaunchKernelGGL(srk::weight_layout_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, w, (int)Co,
-                     (int)Ci, (int)KH, (int)KW, 0, ws);
-  srk::ConvArgs c{};
-  c.N = (int)N; c.H = (int)H; c.W = (int)W; c.Ci = (int)Ci; c.Ho = (int)Ho; c.Wo = (int)Wo; c.Co = (int)Co;
-  c.KH = (int)KH; c.KW = (int)KW; c.ph = (int)ph; c.pw = (int)pw; c.sh = 1; c.sw = 1;
+  srk::launch_weight_layout(w, Co, Ci, KH, KW, 0, ws, s);
+  srk::ConvArgs c = srk::conv_args(N, H, W, Ci, Co, KH, KW, ph, pw, 1, 1, 1, Ho, Wo);
   c.x = x; c.wmat = ws; c.out = y; c.bias = bias;
   c.M = N * Ho * Wo; c.Nn = Co; c.K = KH * KW * Ci;
   c.pool_w = (int)pool_w;
   c.pool_arg = argmax;
   const int prec = srk::matmul_prec();
-  if (srk::s16_ok(prec, Ci, Co, {x, ws, x16})) {
-    const float* src[2] = {x, ws};
-    const int64_t n[2] = {N * H * W * Ci, nw};
-    unsigned short* d16[2] = {static_cast<unsigned short*>(x16), nullptr};
-    const bool ready[2] = {x16_ready, false};
-    if (int rc = srk::to16_all(prec, src, n, 2, d16, s, ready)) return rc;
-    c.a16 = d16[0];
-    c.b16 = d16[1];
-    if (x16 && x16_written) *x16_written = 1;
-    // fbanks_cnn conv2 + maxpool2: the row-staged kernel (weights resident in LDS, 8 image rows per tile)
-    if (srk::g_opt_conv_row16 && KH == 1 && KW == 7 && ph == 0 && pw == 3 && W == 40 && Ci == 64 && Co == 128 &&
-        pool_w == 4 && (N * H) < (1LL << 30) / (W * Ci)) {
-      srk::RowArgs ra{};
-      ra.x16 = c.a16;
-      ra.w16 = c.b16;
-      ra.bias = bias;
-      ra.y = y;
-      ra.arg = argmax;
-      ra.rows = (int)(N * H);
-      ra.groups = (int)((N * H + 7) / 8);
-      srk::ProfScope prof("conv_fwd_lp", s, 2.0 * (double)c.M * (double)c.Nn * (double)c.K);
-      prof.detail("conv_row16_pool_kernel %lldx%lldx%lld", (long long)c.M, (long long)c.Nn, (long long)c.K);
-      prof.bytes(srk::conv_bytes(c, srk::kFwd, 2));
-      const bool w4 = srk::g_opt_conv_row16 == 2;
-      const dim3 grid((unsigned)std::min<int64_t>(ra.groups, srk::kCUs)), block(w4 ? 256 : 512);
-      if (prec == srk::kPrecBF16) {
-        if (w4) hipLaunchKernelGGL((srk::conv_row16_pool_kernel<1, 7, 3, 40, 64, 128, 8, 4>), grid, block, 0, s, ra);
-        else hipLaunchKernelGGL((srk::conv_row16_pool_kernel<1, 7, 3, 40, 64, 128, 8, 8>), grid, block, 0, s, ra);
-      } else {
-        if (w4) hipLaunchKernelGGL((srk::conv_row16_pool_kernel<2, 7, 3, 40, 64, 128, 8, 4>), grid, block, 0, s, ra);
-        else hipLaunchKernelGGL((srk::conv_row16_pool_kernel<2, 7, 3, 40, 64, 128, 8, 8>), grid, block, 0, s, ra);
-      }
-      SRK_CHECK_HIP(hipGetLastError());
-      return SRK_OK;
-    }
+  const srk::RowGrid rg(N * H);
+  if (int rc = srk::fwd_sources16(c, prec, x16, x16_ready, x16_written, s)) return rc;
+  // on 16-bit sources: the row-staged kernel (weights resident in LDS, 8 image rows per tile)
+  if (c.a16 && srk::g_opt_conv_row16 && srk::Conv2::is(c, srk::Conv2::kRows16Fwd)) {
+    srk::RowArgs ra = rg.args<srk::RowArgs>();
+    ra.x16 = c.a16;
+    ra.w16 = c.b16;
+    ra.bias = bias;
+    ra.y = y;
+    ra.arg = argmax;
+    srk::ProfScope prof("conv_fwd_lp", s, 2.0 * (double)c.M * (double)c.Nn * (double)c.K);
+    prof.detail("conv_row16_pool_kernel %lldx%lldx%lld", (long long)c.M, (long long)c.Nn, (long long)c.K);
+    prof.bytes(srk::conv_bytes(c, srk::kFwd, 2));
+    srk::launch_row16_pool(prec, ra, rg, s);
+    SRK_CHECK_HIP(hipGetLastError());
+    return SRK_OK;
   }
-  // fbanks_cnn conv2 + maxpool2 on fp32 operands: the row-staged kernel (weights streamed per tap), unless the
-  // ring pooled forward is asked for (conv_ring bit 7)
-  if (!c.a16 && srk::matmul_prec() == srk::kPrecF32 && srk::g_opt_conv_row32 && !(srk::g_opt_conv_ring & 0x80) &&
-      KH == 1 && KW == 7 && ph == 0 &&
-      pw == 3 && W == 40 && Ci == 64 && Co == 128 && pool_w == 4 && (N * H) < (1LL << 31) / (W * Ci * 4)) {
-    srk::Row32Args ra{};
+  // on fp32 operands: the row-staged kernel (weights streamed per tap), unless the ring pooled forward is asked
+  // for (conv_ring bit 7)
+  if (!c.a16 && prec == srk::kPrecF32 && srk::g_opt_conv_row32 && !(srk::g_opt_conv_ring & 0x80) &&
+      srk::Conv2::is(c, srk::Conv2::kRows32)) {
+    srk::Row32Args ra = rg.args<srk::Row32Args>();
     ra.x = x;
     ra.wt = ws;
     ra.bias = bias;
     ra.y = y;
     ra.arg = argmax;
-    ra.rows = (int)(N * H);
-    ra.groups = (int)((N * H + 7) / 8);
     srk::ProfScope prof("conv_fwd", s, 2.0 * (double)c.M * (double)c.Nn * (double)c.K);
     prof.detail("conv_row32_pool_kernel %lldx%lldx%lld", (long long)c.M, (long long)c.Nn, (long long)c.K);
     prof.bytes(srk::conv_bytes(c, srk::kFwd, 4));
-    hipLaunchKernelGGL((srk::conv_row32_pool_kernel<7, 3, 40, 64, 128, 8>),
-                       dim3((unsigned)std::min<int64_t>(ra.groups, srk::kCUs)), dim3(512), 0, s, ra);
+    hipLaunchKernelGGL((srk::conv_row32_pool_kernel<SRK_C2>), dim3((unsigned)rg.G), dim3(512), 0, s, ra);
     SRK_CHECK_HIP(hipGetLastError());
     return SRK_OK;
   }
-  return srk::run_conv_gemm<srk::kFwd>(c, s, "conv_fwd");
+  return srk::run_conv_gemm<srk::kFwd>(c, s);
   SRK_API_END
 }
 
@@ -3420,8 +3417,8 @@ int srk_conv2d_nhwc_bwd_pool(const float* x, int64_t N, int64_t H, int64_t W, in
   if (srk::g_opt_conv_unpool16 && !full_width && Co % 8 == 0 && srk::s16_ok(prec, Ci, Co, {x, w, x16, ws})) {
     // fbanks_cnn conv2 (Conv2d(64, 128, (1, 7), padding (0, 3)) over W = 40 + MaxPool2d((1, 4))): both gradients from
     // the pooled gradient on the row-staged kernels, no dense dY
-    if (srk::g_opt_conv_row16 && srk::g_opt_conv_row16_dgrad && KH == 1 && KW == 7 && ph == 0 && pw == 3 && W == 40 &&
-        Ci == 64 && Co == 128 && dw && (N * H) < (1LL << 30) / (W * Co))
+    if (srk::g_opt_conv_row16 && srk::g_opt_conv_row16_dgrad && dw &&
+        srk::Conv2::is(srk::conv_args(N, H, W, Ci, Co, KH, KW, ph, pw, 1, 1, 1, Ho, Wo), srk::Conv2::kRows16Bwd))
       return srk::conv2_bwd16_pooled(x, N, H, w, dy_pooled, argmax, dx, dw, db, ws, x16, s);
     // 16-bit-source modes: the dense dY straight as its 16-bit copy, the bias gradient from the pooled
     // gradient (each pooled value sits once in the dense dY, the rest are zeros), then the backward

@@ -17,6 +17,11 @@ from ._lib import call
 from .features import ptr, require_gpu, stream_ptr
 
 
+def _optr(t):
+    """ptr(t) of an optional tensor: None stays None (a null pointer across the C ABI)."""
+    return None if t is None else ptr(t)
+
+
 def _check_cuda(*ts):
     for t in ts:
         if t is not None and (t.device.type != "cuda" or t.dtype != torch.float32):
@@ -91,7 +96,7 @@ class _GRULayerFn(torch.autograd.Function):
         # 16-bit modes: the previous layer's own 16-bit copy of h is this layer's x16 (module note at
         # _copies16); this layer's copy of its output goes to the next layer
         x16 = _copy16_get(x) if IN % 8 == 0 else None
-        call("srk_gru_layer_fwd_x16", ptr(x), ptr(x16) if x16 is not None else None, B, T, IN, H, ptr(w_ih),
+        call("srk_gru_layer_fwd_x16", ptr(x), _optr(x16), B, T, IN, H, ptr(w_ih),
              ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(y), ptr(ws), stream_ptr())
         ctx.x16 = x16
         off = int(_lib.lib().srk_gru_y16_offset(B, T, IN, H)) if _copy16_wanted(2 * H) else -1
@@ -125,8 +130,8 @@ class _GRULayerFn(torch.autograd.Function):
         _copy16_drop(y)   # the next layer's backward has run
         x16, ctx.x16 = ctx.x16, None
         with _lib.precision_scope(ctx.prec):
-            call("srk_gru_layer_bwd_x16", ptr(x), ptr(x16) if x16 is not None else None, B, T, IN, H, ptr(w_ih),
-                 ptr(w_hh), ptr(y), ptr(ws), ptr(dy), ptr(dx) if dx is not None else None, ptr(dw_ih), ptr(dw_hh),
+            call("srk_gru_layer_bwd_x16", ptr(x), _optr(x16), B, T, IN, H, ptr(w_ih),
+                 ptr(w_hh), ptr(y), ptr(ws), ptr(dy), _optr(dx), ptr(dw_ih), ptr(dw_hh),
                  ptr(db_ih), ptr(db_hh), int(acc), ptr(ws2), stream_ptr())
         red = _reducer_of(P[0])
         if red is not None:
@@ -260,7 +265,7 @@ class _PCENFn(torch.autograd.Function):
         B, T, C = x.shape
         y = torch.empty_like(x)
         m = torch.empty_like(x) if grad_on and any(ctx.needs_input_grad[:2]) else None
-        call("srk_pcen_fwd", ptr(x), ptr(p), B, T, C, log_scale, eps, ptr(y), ptr(m) if m is not None else None,
+        call("srk_pcen_fwd", ptr(x), ptr(p), B, T, C, log_scale, eps, ptr(y), _optr(m),
              stream_ptr())
         if m is not None:
             ctx.save_for_backward(x, p, m)
@@ -276,7 +281,7 @@ class _PCENFn(torch.autograd.Function):
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dp = torch.empty_like(p)
         call("srk_pcen_bwd", ptr(x), ptr(p), ptr(m), ptr(dy), B, T, C, log_scale, eps,
-             ptr(dx) if dx is not None else None, ptr(dp), ptr(ws), stream_ptr())
+             _optr(dx), ptr(dp), ptr(ws), stream_ptr())
         return dx, dp, None, None, None, None
 
 
@@ -336,7 +341,7 @@ class _LinearFn(torch.autograd.Function):
         N = w.shape[0]
         y = torch.empty((M, N), device=x.device)
         call("srk_gemm_f32", 0, 1, M, N, K, 1.0, ptr(x), x.stride(0), ptr(w), K, 0.0, ptr(y), N,
-             ptr(b) if b is not None else None, 1 if b is not None else 0, stream_ptr())
+             _optr(b), 1 if b is not None else 0, stream_ptr())
         ctx.save_for_backward(x, w)
         ctx.has_bias = b is not None
         ctx.params = (w_param, b)
@@ -416,7 +421,7 @@ class _CrossEntropyFn(torch.autograd.Function):
         dlogits = torch.empty_like(logits) if ctx.needs_input_grad[0] else None
         ws = torch.empty(B + 1, device=logits.device)
         call("srk_cross_entropy", ptr(logits), ptr(labels), B, C, ptr(loss),
-             ptr(dlogits) if dlogits is not None else None, ptr(ws), stream_ptr())
+             _optr(dlogits), ptr(ws), stream_ptr())
         ctx.save_for_backward(dlogits)
         return loss
 
@@ -483,43 +488,93 @@ def _pair(v):
     return (v, v) if isinstance(v, int) else tuple(v)
 
 
+def _conv_ws(Ci, Co, KH, KW, device):
+    return torch.empty(int(_lib.lib().srk_conv2d_workspace_floats(Ci, Co, KH, KW)), device=device)
+
+
+def _x16_handover(x, Ci, Co, pop, w_needs_grad):
+    """(x16, written) for a conv forward at 16-bit matmul precision with 8-aligned channels: the producer's 16-bit
+    copy of x (written = 2: ready; popped from the table when its producer never drops it), else storage for the
+    library to keep the forward's copy in when the backward will read it (the library reports in ``written``
+    whether it did), else (None, 0)."""
+    x16, written = None, ctypes.c_int(0)
+    if _lib.matmul_precision() != "fp32" and Ci % 8 == 0 and Co % 8 == 0:
+        x16 = _copy16_get(x, pop=pop)
+        if x16 is not None:
+            written.value = 2
+        elif w_needs_grad:
+            x16 = torch.empty(x.numel(), device=x.device, dtype=torch.int16)
+    return x16, written
+
+
+def _dw_target(ctx, w):
+    """(dw, accumulate) of a conv backward: the FlatParams-owned .grad of ctx.w_param, which the kernel that forms
+    the weight gradient ADDS it into (no autograd add kernel), else a fresh tensor returned to autograd."""
+    gw = _flat_grad(ctx.w_param) if ctx.needs_input_grad[1] and INPLACE_GRADS else None
+    return (gw, 1) if gw is not None else (torch.empty_like(w), 0)
+
+
+def _dw_done(ctx, dw, accumulate):
+    """What the backward returns for the weight after the call: None once accumulated in place (the gradient
+    reducer is told), else dw in the parameter's shape."""
+    if not accumulate:
+        return dw.view(ctx.w_param.shape)
+    red = _reducer_of(ctx.w_param)
+    if red is not None:
+        red.mark_ready([ctx.w_param])
+    return None
+
+
+def _conv_operands(x, w, b):
+    """x (channels last) and the weight of a dense conv forward, contiguous and checked."""
+    x, w = x.contiguous(), w.contiguous()
+    _check_cuda(x, w, b)
+    if x.shape[-1] != w.shape[1]:
+        raise _lib.SrkError("conv: input has %d channels, weight expects %d" % (x.shape[-1], w.shape[1]))
+    return x, w
+
+
+def _conv_forward_done(ctx, x, w, w_param, x16, written, geom):
+    """What a dense conv forward leaves for its backward: w as the library saw it, w_param the parameter itself (so
+    the backward can accumulate into its .grad), the 16-bit copy of x if the library kept one."""
+    ctx.x16 = x16 if written.value else None
+    ctx.prec = _lib.matmul_precision()
+    ctx.save_for_backward(x, w)
+    ctx.w_param = w_param
+    ctx.geom = geom
+
+
+def _conv_backward_buffers(ctx, dy, x, w, has_b, KH, KW):
+    """(dy, dy16, dx, dw, accumulate, db, ws, x16) of a dense conv backward."""
+    dy = dy.contiguous()
+    dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+    dw, acc = _dw_target(ctx, w)
+    db = torch.empty((w.shape[0],), device=x.device) if has_b else None
+    ws = _conv_ws(x.shape[-1], w.shape[0], KH, KW, x.device)
+    x16 = ctx.x16 if ctx.prec == _lib.matmul_precision() else None   # a copy in this precision only
+    ctx.x16 = None
+    dy16 = _copy16_get(dy, pop=True)   # the producing BatchNorm backward's copy of dY
+    return dy, dy16, dx, dw, acc, db, ws, x16
+
+
 class _Conv2dNHWCFn(torch.autograd.Function):
+    """Conv2d on channels-last [N, H, W, Ci] (srk_conv2d_nhwc_fwd16 / _bwd16_acc)."""
+
     @staticmethod
     def forward(ctx, x, w, b, padding, stride):
-        # w: the Conv2d weight [Co, Ci, KH, KW], or a Conv1d weight [Co, Ci, K] taken as [Co, Ci, 1, K] (the
-        # parameter itself either way, so the backward can accumulate into its .grad)
-        x = x.contiguous()
-        w_param = w
-        w = w.contiguous()
-        if w.dim() == 3:
-            w = w.unsqueeze(2)
-        _check_cuda(x, w, b)
+        x, wc = _conv_operands(x, w, b)
+        if wc.dim() == 3:   # a Conv1d weight [Co, Ci, K] taken as [Co, Ci, 1, K]
+            wc = wc.unsqueeze(2)
         N, H, W, Ci = x.shape
-        Co, Ci2, KH, KW = w.shape
-        if Ci2 != Ci:
-            raise _lib.SrkError("conv: input has %d channels, weight expects %d" % (Ci, Ci2))
-        ph, pw = padding
-        sh, sw = stride
-        Ho, Wo = (H + 2 * ph - KH) // sh + 1, (W + 2 * pw - KW) // sw + 1
-        y = torch.empty((N, Ho, Wo, Co), device=x.device)
-        ws = torch.empty(int(_lib.lib().srk_conv2d_workspace_floats(Ci, Co, KH, KW)), device=x.device)
-        # 16-bit matmul precision with 8-aligned channels: keep the forward's 16-bit copy of x for the
-        # backward's gathers (srk_conv2d_nhwc_fwd16; the library reports whether it wrote it)
-        x16, written = None, ctypes.c_int(0)
-        if _lib.matmul_precision() != "fp32" and Ci % 8 == 0 and Co % 8 == 0:
-            x16 = _copy16_get(x)   # the producing BatchNorm's copy (written = 2: ready)
-            if x16 is not None:
-                written.value = 2
-            elif ctx.needs_input_grad[1]:
-                x16 = torch.empty(x.numel(), device=x.device, dtype=torch.int16)
-        call("srk_conv2d_nhwc_fwd16", ptr(x), N, H, W, Ci, ptr(w), ptr(b) if b is not None else None, Co, KH, KW,
-             ph, pw, sh, sw, ptr(y), ptr(ws), ptr(x16) if x16 is not None else None, ctypes.byref(written),
-             stream_ptr())
-        ctx.x16 = x16 if written.value else None
-        ctx.prec = _lib.matmul_precision()
-        ctx.save_for_backward(x, w)
-        ctx.w_param = w_param
-        ctx.geom = (padding, stride, b is not None)
+        Co, _, KH, KW = wc.shape
+        (ph, pw), (sh, sw) = padding, stride
+        y = torch.empty((N, (H + 2 * ph - KH) // sh + 1, (W + 2 * pw - KW) // sw + 1, Co), device=x.device)
+        ws = _conv_ws(Ci, Co, KH, KW, x.device)
+        # keep the forward's 16-bit copy of x for the backward's gathers (the library reports whether it wrote it)
+        x16, written = _x16_handover(x, Ci, Co, False, ctx.needs_input_grad[1])
+        call("srk_conv2d_nhwc_fwd16", ptr(x), N, H, W, Ci, ptr(wc), _optr(b), Co, KH, KW, ph, pw, sh, sw, ptr(y),
+             ptr(ws), _optr(x16), ctypes.byref(written), stream_ptr())
+        _conv_forward_done(ctx, x, wc, w, x16, written, (padding, stride, b is not None))
         return y
 
     @staticmethod
@@ -528,28 +583,10 @@ class _Conv2dNHWCFn(torch.autograd.Function):
         (ph, pw), (sh, sw), has_b = ctx.geom
         N, H, W, Ci = x.shape
         Co, _, KH, KW = w.shape
-        dy = dy.contiguous()
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        # the weight gradient ADDED to a FlatParams-owned .grad in the layout kernel (no autograd add kernel)
-        gw = _flat_grad(ctx.w_param) if ctx.needs_input_grad[1] and INPLACE_GRADS else None
-        dw = gw if gw is not None else torch.empty_like(w)
-        db = torch.empty((Co,), device=x.device) if has_b else None
-        ws = torch.empty(int(_lib.lib().srk_conv2d_workspace_floats(Ci, Co, KH, KW)), device=x.device)
-        x16 = ctx.x16 if ctx.prec == _lib.matmul_precision() else None   # a copy in this precision only
-        ctx.x16 = None
-        dy16 = _copy16_get(dy, pop=True)   # the producing BatchNorm backward's copy of dY
+        dy, dy16, dx, dw, acc, db, ws, x16 = _conv_backward_buffers(ctx, dy, x, w, has_b, KH, KW)
         call("srk_conv2d_nhwc_bwd16_acc", ptr(x), N, H, W, Ci, ptr(w), Co, KH, KW, ph, pw, sh, sw, ptr(dy),
-             ptr(dy16) if dy16 is not None else None, ptr(dx) if dx is not None else None, ptr(dw),
-             ptr(db) if db is not None else None, ptr(ws), ptr(x16) if x16 is not None else None,
-             1 if gw is not None else 0, stream_ptr())
-        if gw is not None:
-            red = _reducer_of(ctx.w_param)
-            if red is not None:
-                red.mark_ready([ctx.w_param])
-            dw = None
-        else:
-            dw = dw.view(ctx.w_param.shape)
-        return dx, dw, db, None, None
+             _optr(dy16), _optr(dx), ptr(dw), _optr(db), ptr(ws), _optr(x16), acc, stream_ptr())
+        return dx, _dw_done(ctx, dw, acc), db, None, None
 
 
 class Conv2d(tnn.Module):
@@ -575,31 +612,15 @@ class _Conv1dDilFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b, padding, dilation):
-        x = x.contiguous()
-        w_param = w
-        w = w.contiguous()
-        _check_cuda(x, w, b)
+        x, wc = _conv_operands(x, w, b)
         N, L, Ci = x.shape
-        Co, Ci2, K = w.shape
-        if Ci2 != Ci:
-            raise _lib.SrkError("conv: input has %d channels, weight expects %d" % (Ci, Ci2))
-        Lo = L + 2 * padding - dilation * (K - 1)
-        y = torch.empty((N, max(Lo, 0), Co), device=x.device)
-        ws = torch.empty(int(_lib.lib().srk_conv2d_workspace_floats(Ci, Co, 1, K)), device=x.device)
-        x16, written = None, ctypes.c_int(0)
-        if _lib.matmul_precision() != "fp32" and Ci % 8 == 0 and Co % 8 == 0:
-            x16 = _copy16_get(x)   # the producing BatchNorm's copy (written = 2: ready)
-            if x16 is not None:
-                written.value = 2
-            elif ctx.needs_input_grad[1]:
-                x16 = torch.empty(x.numel(), device=x.device, dtype=torch.int16)
-        call("srk_conv1d_nlc_dil_fwd", ptr(x), N, L, Ci, ptr(w), ptr(b) if b is not None else None, Co, K, padding,
-             dilation, ptr(y), ptr(ws), ptr(x16) if x16 is not None else None, ctypes.byref(written), stream_ptr())
-        ctx.x16 = x16 if written.value else None
-        ctx.prec = _lib.matmul_precision()
-        ctx.save_for_backward(x, w)
-        ctx.w_param = w_param
-        ctx.geom = (padding, dilation, b is not None)
+        Co, _, K = wc.shape
+        y = torch.empty((N, max(L + 2 * padding - dilation * (K - 1), 0), Co), device=x.device)
+        ws = _conv_ws(Ci, Co, 1, K, x.device)
+        x16, written = _x16_handover(x, Ci, Co, False, ctx.needs_input_grad[1])
+        call("srk_conv1d_nlc_dil_fwd", ptr(x), N, L, Ci, ptr(wc), _optr(b), Co, K, padding, dilation, ptr(y), ptr(ws),
+             _optr(x16), ctypes.byref(written), stream_ptr())
+        _conv_forward_done(ctx, x, wc, w, x16, written, (padding, dilation, b is not None))
         return y
 
     @staticmethod
@@ -608,28 +629,10 @@ class _Conv1dDilFn(torch.autograd.Function):
         pad, dil, has_b = ctx.geom
         N, L, Ci = x.shape
         Co, _, K = w.shape
-        dy = dy.contiguous()
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        # the weight gradient ADDED to a FlatParams-owned .grad in the layout kernel (no autograd add kernel)
-        gw = _flat_grad(ctx.w_param) if ctx.needs_input_grad[1] and INPLACE_GRADS else None
-        dw = gw if gw is not None else torch.empty_like(w)
-        db = torch.empty((Co,), device=x.device) if has_b else None
-        ws = torch.empty(int(_lib.lib().srk_conv2d_workspace_floats(Ci, Co, 1, K)), device=x.device)
-        x16 = ctx.x16 if ctx.prec == _lib.matmul_precision() else None   # a copy in this precision only
-        ctx.x16 = None
-        dy16 = _copy16_get(dy, pop=True)   # the producing BatchNorm backward's copy of dY
-        call("srk_conv1d_nlc_dil_bwd", ptr(x), N, L, Ci, ptr(w), Co, K, pad, dil, ptr(dy),
-             ptr(dy16) if dy16 is not None else None, ptr(dx) if dx is not None else None, ptr(dw),
-             ptr(db) if db is not None else None, ptr(ws), ptr(x16) if x16 is not None else None,
-             1 if gw is not None else 0, stream_ptr())
-        if gw is not None:
-            red = _reducer_of(ctx.w_param)
-            if red is not None:
-                red.mark_ready([ctx.w_param])
-            dw = None
-        else:
-            dw = dw.view(ctx.w_param.shape)
-        return dx, dw, db, None, None
+        dy, dy16, dx, dw, acc, db, ws, x16 = _conv_backward_buffers(ctx, dy, x, w, has_b, 1, K)
+        call("srk_conv1d_nlc_dil_bwd", ptr(x), N, L, Ci, ptr(w), Co, K, pad, dil, ptr(dy), _optr(dy16), _optr(dx),
+             ptr(dw), _optr(db), ptr(ws), _optr(x16), acc, stream_ptr())
+        return dx, _dw_done(ctx, dw, acc), db, None, None
 
 
 class Conv1d(tnn.Module):
@@ -683,7 +686,7 @@ class _Conv1PoolFn(torch.autograd.Function):
         # so the library may leave the fp32 y unwritten (it does only when it writes the copy)
         written = ctypes.c_int(3 if (y16_only and y16 is not None) else 0)
         call("srk_conv1_pool_fwd16", ptr(x), N, H, W, ptr(w.contiguous()), ptr(b), Co, KH, KW, padding[0], padding[1],
-             pool, ptr(y), ptr(arg), ptr(y16) if y16 is not None else None, ctypes.byref(written), stream_ptr())
+             pool, ptr(y), ptr(arg), _optr(y16), ctypes.byref(written), stream_ptr())
         if written.value:
             _copy16_put(y, y16)
         ctx.save_for_backward(x, arg, w)
@@ -743,17 +746,11 @@ class _ConvPoolNHWCFn(torch.autograd.Function):
         Ho, Wo = H + 2 * ph - KH + 1, W + 2 * pw - KW + 1
         y = torch.empty((N, Ho, Wo // pool_w, Co), device=x.device)
         arg = torch.empty((N, Ho, Wo // pool_w, Co), device=x.device, dtype=torch.uint8)
-        ws = torch.empty(int(_lib.lib().srk_conv2d_workspace_floats(Ci, Co, KH, KW)), device=x.device)
-        x16, written = None, ctypes.c_int(0)
-        if _lib.matmul_precision() != "fp32" and Ci % 8 == 0 and Co % 8 == 0:
-            x16 = _copy16_get(x, pop=True)   # the producing srk_conv1_pool_fwd16's copy (written = 2: ready)
-            if x16 is not None:
-                written.value = 2
-            elif ctx.needs_input_grad[1]:
-                x16 = torch.empty(x.numel(), device=x.device, dtype=torch.int16)
-        call("srk_conv2d_nhwc_fwd_pool", ptr(x), N, H, W, Ci, ptr(w), ptr(b) if b is not None else None, Co, KH, KW,
-             ph, pw, pool_w, ptr(y), ptr(arg), ptr(ws), ptr(x16) if x16 is not None else None, ctypes.byref(written),
-             stream_ptr())
+        ws = _conv_ws(Ci, Co, KH, KW, x.device)
+        # the producing srk_conv1_pool_fwd16's copy is popped: nothing else drops its entry
+        x16, written = _x16_handover(x, Ci, Co, True, ctx.needs_input_grad[1])
+        call("srk_conv2d_nhwc_fwd_pool", ptr(x), N, H, W, Ci, ptr(w), _optr(b), Co, KH, KW, ph, pw, pool_w, ptr(y),
+             ptr(arg), ptr(ws), _optr(x16), ctypes.byref(written), stream_ptr())
         ctx.x16 = x16 if written.value else None
         ctx.prec = _lib.matmul_precision()
         ctx.save_for_backward(x, w, arg)
@@ -770,12 +767,11 @@ class _ConvPoolNHWCFn(torch.autograd.Function):
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dw = torch.empty_like(w)
         db = torch.empty((Co,), device=x.device) if has_b else None
-        ws = torch.empty(int(_lib.lib().srk_conv2d_workspace_floats(Ci, Co, KH, KW)), device=x.device)
+        ws = _conv_ws(Ci, Co, KH, KW, x.device)
         x16 = ctx.x16 if ctx.prec == _lib.matmul_precision() else None
         ctx.x16 = None
         call("srk_conv2d_nhwc_bwd_pool", ptr(x), N, H, W, Ci, ptr(w), Co, KH, KW, ph, pw, pool_w, ptr(dy), ptr(arg),
-             ptr(dx) if dx is not None else None, ptr(dw), ptr(db) if db is not None else None, ptr(ws),
-             ptr(x16) if x16 is not None else None, stream_ptr())
+             _optr(dx), ptr(dw), _optr(db), ptr(ws), _optr(x16), stream_ptr())
         return dx, dw, db, None, None
 
 
@@ -859,8 +855,8 @@ class _DepthwiseConv2dFn(torch.autograd.Function):
         (ph, pw), (sh, sw) = padding, stride
         Ho, Wo = (H + 2 * ph - KH) // sh + 1, (W + 2 * pw - KW) // sw + 1
         y = torch.empty((N, max(Ho, 0), max(Wo, 0), C), device=x.device)
-        call("srk_dwconv2d_nhwc_fwd", ptr(x), N, H, W, C, ptr(w), ptr(b) if b is not None else None, KH, KW, ph, pw,
-             sh, sw, ptr(y), stream_ptr())
+        call("srk_dwconv2d_nhwc_fwd", ptr(x), N, H, W, C, ptr(w), _optr(b), KH, KW, ph, pw, sh, sw, ptr(y),
+             stream_ptr())
         ctx.save_for_backward(x, w)
         ctx.w_param = w_param
         ctx.geom = (padding, stride, b is not None)
@@ -875,20 +871,13 @@ class _DepthwiseConv2dFn(torch.autograd.Function):
         dy = dy.contiguous()
         _copy16_drop(dy)   # the producing BatchNorm backward's 16-bit copy of dY, which only a dense conv reads
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        gw = _flat_grad(ctx.w_param) if ctx.needs_input_grad[1] and INPLACE_GRADS else None
-        dw = gw if gw is not None else torch.empty_like(w)
+        dw, acc = _dw_target(ctx, w)
         db = torch.empty((C,), device=x.device) if has_b else None
         ws = torch.empty(int(_lib.lib().srk_dwconv2d_workspace_floats(N, H, W, C, KH, KW, ph, pw, sh, sw)),
                          device=x.device)
-        call("srk_dwconv2d_nhwc_bwd", ptr(x), N, H, W, C, ptr(w), KH, KW, ph, pw, sh, sw, ptr(dy),
-             ptr(dx) if dx is not None else None, ptr(dw), ptr(db) if db is not None else None, ptr(ws),
-             1 if gw is not None else 0, stream_ptr())
-        if gw is not None:
-            red = _reducer_of(ctx.w_param)
-            if red is not None:
-                red.mark_ready([ctx.w_param])
-            dw = None
-        return dx, dw, db, None, None
+        call("srk_dwconv2d_nhwc_bwd", ptr(x), N, H, W, C, ptr(w), KH, KW, ph, pw, sh, sw, ptr(dy), _optr(dx), ptr(dw),
+             _optr(db), ptr(ws), acc, stream_ptr())
+        return dx, _dw_done(ctx, dw, acc), db, None, None
 
 
 class DepthwiseConv2d(tnn.Module):
@@ -1077,9 +1066,8 @@ class _BatchNormFn(torch.autograd.Function):
         if relu and RELU_MASK and any(ctx.needs_input_grad[:4]):
             mask = torch.empty(M * C // 4, device=x.device, dtype=torch.uint8)
         call("srk_batchnorm_fwd16_mask", ptr(x), M, C, ptr(gamma), ptr(beta), float(eps), float(momentum),
-             int(training), ptr(running_mean), ptr(running_var), ptr(res) if res is not None else None, int(relu),
-             ptr(y), ptr(y16) if y16 is not None else None, ctypes.byref(written),
-             ptr(mask) if mask is not None else None, ptr(mean), ptr(invstd), stream_ptr())
+             int(training), ptr(running_mean), ptr(running_var), _optr(res), int(relu), ptr(y), _optr(y16),
+             ctypes.byref(written), _optr(mask), ptr(mean), ptr(invstd), stream_ptr())
         if written.value:
             _copy16_put(y, y16)
         ctx.mask = mask
@@ -1109,10 +1097,9 @@ class _BatchNormFn(torch.autograd.Function):
         gb = _flat_grad(bp) if ctx.needs_input_grad[2] and INPLACE_GRADS else None
         acc = gg is not None and gb is not None
         mask, ctx.mask = ctx.mask, None
-        call("srk_batchnorm_bwd16_mask", ptr(x), ptr(y), ptr(mask) if mask is not None else None, ptr(dy), M, C,
-             ptr(gamma), ptr(mean), ptr(invstd), training, relu, ptr(dx) if dx is not None else None,
-             ptr(dx16) if dx16 is not None else None, ctypes.byref(written), ptr(dgamma), ptr(dbeta),
-             ptr(dres) if dres is not None else None, ptr(gg) if acc else None, ptr(gb) if acc else None, stream_ptr())
+        call("srk_batchnorm_bwd16_mask", ptr(x), ptr(y), _optr(mask), ptr(dy), M, C,
+             ptr(gamma), ptr(mean), ptr(invstd), training, relu, _optr(dx), _optr(dx16), ctypes.byref(written),
+             ptr(dgamma), ptr(dbeta), _optr(dres), ptr(gg) if acc else None, ptr(gb) if acc else None, stream_ptr())
         if written.value:
             _copy16_put(dx, dx16)
         if acc:
@@ -1210,7 +1197,7 @@ class _SyncBatchNormFn(torch.autograd.Function):
         y = torch.empty_like(x)
         res = residual.contiguous() if residual is not None else None
         call("srk_batchnorm_apply", ptr(x), M, C, ptr(mean), ptr(invstd), ptr(gamma), ptr(beta),
-             ptr(res) if res is not None else None, int(relu), ptr(y), stream_ptr())
+             _optr(res), int(relu), ptr(y), stream_ptr())
         ctx.save_for_backward(x, y, gamma, mean, invstd, total)
         ctx.flags = (int(relu), residual is not None)
         ctx.group = group
@@ -1233,8 +1220,7 @@ class _SyncBatchNormFn(torch.autograd.Function):
         dres = torch.empty_like(x) if has_res and ctx.needs_input_grad[3] else None
         if dx is not None or dres is not None:
             call("srk_batchnorm_bwd_dx", ptr(x), ptr(y), ptr(dy), M, C, ptr(total), ptr(gamma), ptr(mean), ptr(invstd),
-                 ptr(sums), relu, ptr(dx) if dx is not None else None, ptr(dres) if dres is not None else None,
-                 stream_ptr())
+                 ptr(sums), relu, _optr(dx), _optr(dres), stream_ptr())
         return dx, dgamma, dbeta, dres, None, None, None, None, None, None
 
 
