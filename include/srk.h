@@ -276,6 +276,32 @@ int srk_gru_layer_bwd_x16(const float* x, const void* x16, int64_t B, int64_t T,
                           const float* w_ih, const float* w_hh, const float* y, const float* ws_fwd, const float* dy,
                           float* dx, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, int accumulate,
                           float* ws, void* stream);
+/* The TOP layer of a model that reads only the last step, fc(y[:, T-1, :]) (model_mfcc_bgru.py:43-44): the
+ * _x16 pair with y_last [B, 2H] = y[:, T-1, :] as the output and dy_last [B, 2H] as the incoming gradient.
+ * Row T-1 of the reverse direction is its FIRST step (one cell from h = 0), and in the backward its dgi is zero
+ * at every t < T-1, its dgh zero everywhere and dW_hh[1] = 0.  *mode reports what the forward did and goes to
+ * the backward unchanged:
+ *   0  the full layer, exactly srk_gru_layer_fwd_x16 / _bwd_x16 on dy = (zeros, dy_last): every 16-bit
+ *      precision, H != 512, and whenever the persistent recurrence kernels do not run;
+ *   1  fp32 persistent path: the full forward; the backward GEMMs (dW_ih, dW_hh, dx) without their identically
+ *      zero reverse-direction parts (option "gru_top_last" = 1);
+ *   2  also the reverse direction as its one cell each way, the recurrence launches running the forward
+ *      direction only, the input projection its 3H columns plus B rows of the reverse one ("gru_top_last" = 2).
+ *      The reverse half of y at t < T-1 is then NOT written: y is the backward's h_prev source only.  The pruned
+ *      dW_ih / dx sums run in another order than the full layer's: results differ from mode 0 by fp32 rounding.
+ *   3  mode 2's forward, recurrence launches, cells and forward-only dW_hh, with the reverse dgi rows zero-filled
+ *      and the full dW_ih / dx GEMMs kept: every sum runs in the full layer's order, so y_last and all gradients
+ *      are bit for bit mode 0's wherever the layer's input projection runs as one unsplit GEMM (default).
+ * dW_hh[1] is zero-filled (accumulate = 0) or left alone (accumulate = 1).
+ * ws: srk_gru_top_last_workspace_floats(.., backward) floats each way.                                    */
+int64_t srk_gru_top_last_workspace_floats(int64_t B, int64_t T, int64_t in, int64_t H, int backward);
+int srk_gru_top_last_fwd(const float* x, const void* x16, int64_t B, int64_t T, int64_t in, int64_t H,
+                         const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* y,
+                         float* y_last, float* ws, int* mode, void* stream);
+int srk_gru_top_last_bwd(const float* x, const void* x16, int64_t B, int64_t T, int64_t in, int64_t H,
+                         const float* w_ih, const float* w_hh, const float* y, const float* ws_fwd,
+                         const float* dy_last, int mode, float* dx, float* dw_ih, float* dw_hh, float* db_ih,
+                         float* db_hh, int accumulate, float* ws, void* stream);
 
 /* ---------------------------------------------------------------- K6: convolution / pooling
  * nn.Conv2d / nn.Conv1d (zero padding ph/pw, stride sh/sw, no groups — depthwise: srk_dwconv2d_nhwc_*; dilation: srk_conv1d_nlc_dil_*) as implicit GEMM

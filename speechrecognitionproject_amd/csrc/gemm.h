@@ -27,6 +27,12 @@ struct GemmDesc {
   // operand bytes).  No fused row sums on this path.
   const uint16_t* A16 = nullptr;
   const uint16_t* B16 = nullptr;
+  // A launch that computes PART of a larger GEMM and must give its elements that GEMM's bits (an element's sum
+  // order depends on the kernel and the K split, not on the tile grid): no_split = never split K (the larger GEMM
+  // is known not to); plan_batch > 1 = choose the kernel and the K split as the batched launch of plan_batch
+  // such products would, while running `batch` of them.
+  bool no_split = false;
+  int plan_batch = 0;
 };
 
 // Enqueue on `stream`; returns SRK_OK or an srk_status.

@@ -1328,7 +1328,7 @@ int launch_skinny_rnd(const GemmDesc& d, int kind, hipStream_t s) {
 // Which skinny kernel takes this GEMM (-1: none; the matrix-core tiles run it).  Sizes keep each
 // kernel's per-thread loop short and its streamed operand a few MB at most.
 int skinny_kind(const GemmDesc& d) {
-  if (!g_opt_gemm_skinny || d.batch != 1 || d.A16 || d.B16 || d.K <= 0) return -1;
+  if (!g_opt_gemm_skinny || d.batch != 1 || d.plan_batch > 1 || d.A16 || d.B16 || d.K <= 0) return -1;
   if (d.N <= 16 && !d.ta && d.M <= 65535 * 16 && d.M * d.K <= (int64_t)1 << 24) return 0;
   if (d.M <= 16 && !d.tb && d.K <= 1024 && d.N * d.K <= (int64_t)1 << 24) return 1;
   if (d.K <= 16 && !d.tb && d.M <= 65535 && d.M * d.N <= (int64_t)1 << 24) return 2;
@@ -1761,8 +1761,9 @@ int plan_launch(const GemmDesc& d, int BM, int BN, int BK, int per_cu, KernelArg
                              : std::max(1, (int)std::lround(std::sqrt(32.0 * per_cu * BN / (double)BM)));
   ka.remap = remap;
   // Split K when the output grid leaves resident slots idle and K is long (tile::choose_splits).
-  const bool can_split = allow_split && (d.batch == 1 || split_batched);
-  int splits = can_split ? choose_splits(tm * tn * d.batch, d.K, BK, slots, 16) : 1;
+  const int pb = std::max(d.batch, d.plan_batch);   // the batch the plan is made for (GemmDesc::plan_batch)
+  const bool can_split = allow_split && !d.no_split && (pb == 1 || split_batched);
+  int splits = can_split ? choose_splits(tm * tn * pb, d.K, BK, slots, 16) : 1;
   static const int splits_env = env_int("SRK_GEMM_SPLITS", 0);   // A/B measurements only
   if (splits_env > 0 && d.batch == 1 && d.K >= (int64_t)splits_env * 4 * BK) splits = splits_env;
   ka.kchunk = splits > 1 ? ((d.K + splits - 1) / splits + BK - 1) / BK * BK : std::max<int64_t>(d.K, 1);
@@ -1938,11 +1939,12 @@ template <bool TA, bool TB>
 int launch_p32(const GemmDesc& d, hipStream_t s) {
   KernelArgs ka;
   int splits = 1;
-  const int64_t tiles = ((d.M + 255) / 256) * ((d.N + 255) / 256) * d.batch;
+  const int pb = std::max(d.batch, d.plan_batch);
+  const int64_t tiles = ((d.M + 255) / 256) * ((d.N + 255) / 256) * pb;
   const int64_t ki = (d.K + kP32BK - 1) / kP32BK;
   // stream-K where one round of 256 x 256 tiles leaves CUs idle but covers at least half of them
   // (dx of the BiGRU layers: 204 tiles on 256 CUs), K long enough to split
-  const bool streamk = g_opt_gemm_streamk && d.batch == 1 && !d.rowsum && tiles < kCUs && tiles * 2 >= kCUs && ki >= 32;
+  const bool streamk = g_opt_gemm_streamk && pb == 1 && !d.no_split && !d.rowsum && tiles < kCUs && tiles * 2 >= kCUs && ki >= 32;
   if (int rc = plan_launch(d, 256, 256, kP32BK, 1, ka, &splits, !streamk && tiles * 2 < kCUs, true)) return rc;
   if (streamk) {
     ka.sk_wgs = kCUs;
@@ -1971,7 +1973,7 @@ int dispatch_tile(const GemmDesc& d, hipStream_t s, bool vec) {
   // 8 % slower on the x W^T projection (NT) and on the 12-tile dW_hh grid (split 16); batched
   // launches (the BiGRU's two dW_hh) and row sums over a batch only exist on the ping-pong kernel
   const int kern32 = g_opt_gemm32_kernel ? g_opt_gemm32_kernel
-                                         : (!TB && ((d.M >= 2048 && d.N >= 1024) || d.batch > 1) ? 2 : 1);
+                                         : (!TB && ((d.M >= 2048 && d.N >= 1024) || d.batch > 1 || d.plan_batch > 1) ? 2 : 1);
   SRK_REQUIRE(!d.rowsum || d.batch == 1 || (p32_ok && kern32 == 2), SRK_ERR_INVALID,
               "gemm: batched row sums need the fp32 ping-pong kernel (16-B operand rows)");
   if (p32_ok && kern32 == 2) return launch_p32<TA, TB>(d, s);

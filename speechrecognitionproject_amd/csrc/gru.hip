@@ -54,8 +54,6 @@ struct GruArgs {
   float* dhz;           // [2][B][H]
 };
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // Native 4-float vector: HIP's float4 is a struct whose copies lower to memcpy, which SROA cannot
 // keep in registers (a float4 staging array ends up in scratch); ext_vector loads/stores do not.
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -287,6 +285,91 @@ __global__ __launch_bounds__(256) void gru_bwd_step_kernel(GruArgs a, int step) 
     }
     *dhz = dh * zg;
   }
+}
+
+// ------------------------------------------------------------------ last-step top layer (srk_gru_top_last_*)
+// A top layer whose consumer reads row T-1 of y only (fc(last_step(gru(x)[0])), model_mfcc_bgru.py:43-44).
+// y_last[b][:] = y[b][T-1][:]  (C = 2H)
+__global__ void gather_last_kernel(const float* __restrict__ y, int64_t B, int T, int C, float* __restrict__ y_last) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * C) return;
+  const int64_t b = i / C;
+  y_last[i] = y[(b * T + T - 1) * C + (i - b * C)];
+}
+// dy[b][t][:] = t == T - 1 ? dy_last[b][:] : 0: the [B][T][2H] gradient the backward recurrence reads (4 | C)
+__global__ void pad_last_kernel(const float* __restrict__ dy_last, int64_t B, int T, int C, float* __restrict__ dy) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, c4 = C / 4;
+  if (i >= B * T * c4) return;
+  const int64_t row = i / c4, b = row / T;
+  const int c = (int)(i - row * c4) * 4;
+  v4f v = v4f{0.f, 0.f, 0.f, 0.f};
+  if (row - b * T == T - 1) {
+    const float* s = dy_last + b * C + c;
+    v = v4f{s[0], s[1], s[2], s[3]};
+  }
+  st4(dy + i * 4, v);
+}
+// X[r][c0 .. c0 + cols) = 0 for r < rows (4 | cols, c0, ld): the reverse direction's dgi columns, which the
+// forward-only backward recurrence leaves unwritten, ahead of GEMMs that read whole rows
+__global__ void zero_cols_kernel(float* __restrict__ X, int64_t rows, int cols, int c0, int ld) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, c4 = cols / 4;
+  if (i >= rows * c4) return;
+  const int64_t r = i / c4;
+  st4(X + r * ld + c0 + (i - r * c4) * 4, v4f{0.f, 0.f, 0.f, 0.f});
+}
+// The reverse direction's row T-1 is its FIRST step: one cell from h = 0, so gh = b_hh and h = (1 - z) n (the
+// arithmetic of the persistent kernels' step 0, cell functions included: FAST as gru_fp32_fast_cell()).  Reads
+// gi[(b, T-1)][3H:6H]; writes y[b][T-1][H:2H], the whole y_last row (its forward half copied from y) and the saved
+// gates of (dir 1, t = T-1) unit-interleaved (store_gates_il's layout), as the backward reads them.
+template <bool FAST>
+__global__ void rev_cell_fwd_kernel(const float* __restrict__ gi, const float* __restrict__ b_hh, int64_t B, int T,
+                                    int H, float* __restrict__ y, float* __restrict__ y_last,
+                                    float* __restrict__ gates) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * H) return;
+  const int64_t b = i / H, row = b * T + T - 1;
+  const int j = (int)(i - b * H);
+  const float* g = gi + row * 6 * H + 3 * H;
+  const float bhr = b_hh[3 * H + j], bhz = b_hh[4 * H + j], ghn = b_hh[5 * H + j];
+  float rg, zg, ng;
+  if (FAST) {
+    rg = sigmoid_fast(g[j] + bhr);
+    zg = sigmoid_fast(g[H + j] + bhz);
+    ng = tanh_fast(g[2 * H + j] + rg * ghn);
+  } else {
+    rg = sigmoidf_(g[j] + bhr);
+    zg = sigmoidf_(g[H + j] + bhz);
+    ng = tanhf(g[2 * H + j] + rg * ghn);
+  }
+  const float h = (1.0f - zg) * ng;
+  y[row * 2 * H + H + j] = h;
+  y_last[b * 2 * H + H + j] = h;
+  y_last[b * 2 * H + j] = y[row * 2 * H + j];
+  st4(gates + (((int64_t)T + T - 1) * B + b) * 4 * H + 4 * j, v4f{rg, zg, ng, ghn});
+}
+// Its backward: the cell derivatives at h_prev = 0 from dy_last[:, H:], written where the full backward recurrence
+// leaves them: dgi[(b, T-1)][3H:6H] = (dar, daz, dan) and dgh_edge[1][b] = (dar, daz, dan r).
+__global__ void rev_cell_bwd_kernel(const float* __restrict__ gates, const float* __restrict__ dy_last, int64_t B, int T,
+                                    int H, float* __restrict__ dgi, float* __restrict__ dgh_edge) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * H) return;
+  const int64_t b = i / H;
+  const int j = (int)(i - b * H);
+  const v4f gv = ld4(gates + (((int64_t)T + T - 1) * B + b) * 4 * H + 4 * j);
+  const float rg = gv.x, zg = gv.y, ng = gv.z, ghn = gv.w;
+  const float dh = dy_last[b * 2 * H + H + j];
+  const float dn = dh * (1.0f - zg);
+  const float daz = dh * (0.f - ng) * zg * (1.0f - zg);
+  const float dan = dn * (1.0f - ng * ng);
+  const float dar = dan * ghn * rg * (1.0f - rg);
+  float* d = dgi + (b * T + T - 1) * 6 * H + 3 * H;
+  d[j] = dar;
+  d[H + j] = daz;
+  d[2 * H + j] = dan;
+  float* e = dgh_edge + (B + b) * 3 * H;
+  e[j] = dar;
+  e[H + j] = daz;
+  e[2 * H + j] = dan * rg;
 }
 
 int check_dims(int64_t B, int64_t T, int64_t in, int64_t H) {
@@ -540,13 +623,25 @@ int64_t srk_gru_y16_offset(int64_t B, int64_t T, int64_t in, int64_t H) {
   return pad_end(B, T, in, H, 0) + up64(BT * in8 / 2 + 1) + up64(6 * H * in8 / 2 + 1);
 }
 
-int srk_gru_layer_fwd_x16(const float* x, const void* x16_in, int64_t B, int64_t T, int64_t in, int64_t H,
-                          const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* y,
-                          float* ws, void* stream) {
-  SRK_API_BEGIN
-  if (int rc = srk::check_dims(B, T, in, H)) return rc;
-  SRK_REQUIRE(x && w_ih && w_hh && b_ih && b_hh && y && ws, SRK_ERR_INVALID, "gru_fwd: null pointer");
-  hipStream_t s = srk::as_stream(stream);
+// The fp32 persistent path of this layer: both directions' recurrences on the persistent kernels (or neither: they
+// hand the saved gates over unit-interleaved, the per-step kernels in the plain layout).
+static bool persistent_pair(int64_t B, int64_t T, int64_t H) {
+  return srk::g_opt_gru_persistent && srk::gru_persistent_supported(B, T, H, false) &&
+         srk::gru_persistent_supported(B, T, H, true);
+}
+// How srk_gru_top_last_* run a layer (option gru_top_last): modes 1 .. 3 on the fp32 persistent path only (H = 512);
+// everywhere else 0 = the full layer, exactly what srk_gru_layer_* compute.
+static bool top_last_path(int64_t B, int64_t T, int64_t H) {
+  return srk::matmul_prec() == srk::kPrecF32 && H == 512 && persistent_pair(B, T, H);
+}
+static int top_last_mode(int64_t B, int64_t T, int64_t H) { return top_last_path(B, T, H) ? srk::g_opt_gru_top_last : 0; }
+
+// One layer forward.  top_last >= 2 (top_last_mode, with y_last): only row T-1 of y is used, so the reverse direction
+// is its one cell at t = T-1 (rev_cell_fwd_kernel) and its rows t < T-1 of gi / y / the gates are never written.
+static int layer_fwd(const float* x, const void* x16_in, int64_t B, int64_t T, int64_t in, int64_t H,
+                     const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* y,
+                     float* ws, int top_last, float* y_last, hipStream_t s) {
+  const bool rev_cell = top_last >= 2;
   float* gi = ws;
   float* gates = ws + B * T * 6 * H;
   uint16_t* y16 = nullptr;
@@ -592,18 +687,28 @@ int srk_gru_layer_fwd_x16(const float* x, const void* x16_in, int64_t B, int64_t
     xa = xp;
     wa = wp;
   }
-  // both directions of the layer persistent or neither: the persistent fp32 kernels hand the saved
-  // gates over unit-interleaved, the per-step kernels in the plain layout
-  const bool persistent = srk::g_opt_gru_persistent && srk::gru_persistent_supported(B, T, H, false) &&
-                          srk::gru_persistent_supported(B, T, H, true);
+  const bool persistent = persistent_pair(B, T, H);
+  SRK_REQUIRE(!rev_cell || (persistent && y_last), SRK_ERR_INTERNAL, "gru_fwd: rev_cell off the persistent path");
   const bool fuse = persistent && in <= srk::kFusedIn;   // the kernel projects the input itself
   if (!fuse) {
-    GemmDesc g;   // gi[B*T, 6H] = x[B*T, in] * W_ih_cat[6H, in]^T + b_ih_cat
-    g.M = B * T; g.N = 6 * H; g.K = ink;
+    // gi[B*T, 6H] = x[B*T, in] * W_ih_cat[6H, in]^T + b_ih_cat (rev_cell: the forward direction's 3H columns)
+    GemmDesc g;
+    g.M = B * T; g.N = rev_cell ? 3 * H : 6 * H; g.K = ink;
     g.A = xa; g.lda = ink;
     g.B = wa; g.ldb = ink; g.tb = true;
     g.C = gi; g.ldc = 6 * H;
     g.bias = b_ih; g.bias_mode = 1;
+    if (int rc = srk::gemm_f32(g, s)) return rc;
+  }
+  if (rev_cell) {
+    // gi[(b, T-1)][3H:6H] = x[b, T-1, :] * W_ih[1]^T + b_ih[1]: B strided rows, where the full GEMM puts them
+    GemmDesc g;
+    g.M = B; g.N = 3 * H; g.K = ink;
+    g.A = xa + (T - 1) * ink; g.lda = T * ink;
+    g.B = wa + 3 * H * ink; g.ldb = ink; g.tb = true;
+    g.C = gi + (T - 1) * 6 * H + 3 * H; g.ldc = T * 6 * H;
+    g.bias = b_ih + 3 * H; g.bias_mode = 1;
+    g.no_split = top_last == 3;   // mode 3: the full projection's sum order (wherever that GEMM runs unsplit)
     if (int rc = srk::gemm_f32(g, s)) return rc;
   }
   if (persistent) {
@@ -613,7 +718,19 @@ int srk_gru_layer_fwd_x16(const float* x, const void* x16_in, int64_t B, int64_t
     if (fuse) { p.x_in = x; p.w_ih = w_ih; p.b_ih = b_ih; p.in = (int)in; }
     p.xbuf = ws + fwd_xbuf_off(B, T, H);
     p.counters = reinterpret_cast<unsigned*>(ws + fwd_counter_off(B, T, H));
-    return srk::gru_persistent_launch(p, false, s);
+    p.one_dir = rev_cell ? 1 : 0;
+    if (int rc = srk::gru_persistent_launch(p, false, s)) return rc;
+    if (rev_cell) {   // after the recurrence: y_last's forward half is its last step
+      const dim3 grid((unsigned)((B * H + 255) / 256));
+      if (srk::gru_fp32_fast_cell())
+        hipLaunchKernelGGL(srk::rev_cell_fwd_kernel<true>, grid, dim3(256), 0, s, gi, b_hh, B, (int)T, (int)H, y,
+                           y_last, gates);
+      else
+        hipLaunchKernelGGL(srk::rev_cell_fwd_kernel<false>, grid, dim3(256), 0, s, gi, b_hh, B, (int)T, (int)H, y,
+                           y_last, gates);
+      SRK_CHECK_HIP(hipGetLastError());
+    }
+    return SRK_OK;
   }
   srk::GruArgs a{};
   a.B = (int)B; a.T = (int)T; a.H = (int)H; a.in = (int)in;
@@ -627,6 +744,39 @@ int srk_gru_layer_fwd_x16(const float* x, const void* x16_in, int64_t B, int64_t
   }
   SRK_CHECK_HIP(hipGetLastError());
   return SRK_OK;
+}
+
+int srk_gru_layer_fwd_x16(const float* x, const void* x16_in, int64_t B, int64_t T, int64_t in, int64_t H,
+                          const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* y,
+                          float* ws, void* stream) {
+  SRK_API_BEGIN
+  if (int rc = srk::check_dims(B, T, in, H)) return rc;
+  SRK_REQUIRE(x && w_ih && w_hh && b_ih && b_hh && y && ws, SRK_ERR_INVALID, "gru_fwd: null pointer");
+  return layer_fwd(x, x16_in, B, T, in, H, w_ih, w_hh, b_ih, b_hh, y, ws, 0, nullptr, srk::as_stream(stream));
+  SRK_API_END
+}
+
+int64_t srk_gru_top_last_workspace_floats(int64_t B, int64_t T, int64_t in, int64_t H, int backward) {
+  return srk_gru_workspace_floats(B, T, in, H, backward) + (backward ? up64(B * T * 2 * H) : 0);
+}
+
+int srk_gru_top_last_fwd(const float* x, const void* x16_in, int64_t B, int64_t T, int64_t in, int64_t H,
+                         const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* y,
+                         float* y_last, float* ws, int* mode, void* stream) {
+  SRK_API_BEGIN
+  if (int rc = srk::check_dims(B, T, in, H)) return rc;
+  SRK_REQUIRE(x && w_ih && w_hh && b_ih && b_hh && y && y_last && ws && mode, SRK_ERR_INVALID,
+              "gru_top_last_fwd: null pointer");
+  hipStream_t s = srk::as_stream(stream);
+  *mode = top_last_mode(B, T, H);
+  if (int rc = layer_fwd(x, x16_in, B, T, in, H, w_ih, w_hh, b_ih, b_hh, y, ws, *mode, y_last, s)) return rc;
+  if (*mode < 2) {   // modes 0 and 1 ran the full layer: y_last is its row T-1
+    const int64_t n = B * 2 * H;
+    hipLaunchKernelGGL(srk::gather_last_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, y, B, (int)T,
+                       (int)(2 * H), y_last);
+    SRK_CHECK_HIP(hipGetLastError());
+  }
+  return SRK_OK;
   SRK_API_END
 }
 
@@ -638,15 +788,16 @@ int srk_gru_layer_bwd(const float* x, int64_t B, int64_t T, int64_t in, int64_t 
                                accumulate, ws, stream);
 }
 
-int srk_gru_layer_bwd_x16(const float* x, const void* x16_in, int64_t B, int64_t T, int64_t in, int64_t H,
-                          const float* w_ih, const float* w_hh, const float* y, const float* ws_fwd, const float* dy,
-                          float* dx, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, int accumulate,
-                          float* ws, void* stream) {
-  SRK_API_BEGIN
-  if (int rc = srk::check_dims(B, T, in, H)) return rc;
-  SRK_REQUIRE(x && w_ih && w_hh && y && ws_fwd && dy && dw_ih && dw_hh && db_ih && db_hh && ws, SRK_ERR_INVALID,
-              "gru_bwd: null pointer");
-  hipStream_t s = srk::as_stream(stream);
+// One layer backward.  top_last (srk_gru_top_last_bwd, the forward's top_last_mode): dy is zero but for its rows
+// (b, T-1) = dy_last, so after the recurrence the reverse direction's dgi is zero but for those B rows, its dgh is
+// zero everywhere (the live step has h_prev = 0: its dgh sits in dgh_edge[1]) and dW_hh[1] = 0.  Modes 1 and 2 issue
+// only the GEMM work that is not identically zero; modes 2 and 3 replace the reverse recurrence by its one cell
+// (rev_cell_bwd_kernel), leaving dgh[1] (and in mode 2 the reverse dgi rows t < T-1) unwritten and unread.  Mode 3
+// zero-fills those dgi rows and keeps the full dW_ih / dx GEMMs: every result then has the full layer's bits.
+static int layer_bwd(const float* x, const void* x16_in, int64_t B, int64_t T, int64_t in, int64_t H,
+                     const float* w_ih, const float* w_hh, const float* y, const float* ws_fwd, const float* dy,
+                     const float* dy_last, int top_last, float* dx, float* dw_ih, float* dw_hh, float* db_ih,
+                     float* db_hh, int accumulate, float* ws, hipStream_t s) {
   const int64_t BT = B * T;
   if (use_h16(B, T, in, H)) {
     // 16-bit path: the kernel writes dgi16 / dgh16 (aliasing the fp32 dgi region) and the bias-
@@ -756,14 +907,27 @@ int srk_gru_layer_bwd_x16(const float* x, const void* x16_in, int64_t B, int64_t
   a.dy = dy; a.dgi = dgi; a.dgh = dgh; a.dgh_edge = dgh_edge; a.dhz = dhz;
   a.G = (int)((B + srk::kRows - 1) / srk::kRows);
   a.S = (int)(H / srk::kUnits);
-  if (srk::g_opt_gru_persistent && srk::gru_persistent_supported(B, T, H, false) &&
-      srk::gru_persistent_supported(B, T, H, true)) {   // as the forward decided (the gates' layout)
+  const bool persistent = persistent_pair(B, T, H);   // as the forward decided (the gates' layout)
+  SRK_REQUIRE(!top_last || (persistent && dy_last), SRK_ERR_INTERNAL, "gru_bwd: top_last off the persistent path");
+  if (persistent) {
     srk::GruPArgs p{};
     p.B = (int)B; p.T = (int)T; p.H = (int)H;
     p.w_hh = w_hh; p.y_in = y; p.gates = a.gates; p.dy = dy; p.dgi = dgi; p.dgh = dgh; p.dgh_edge = dgh_edge;
     p.xbuf = ws + bwd_xbuf_off(B, T, H);
     p.counters = reinterpret_cast<unsigned*>(ws + bwd_counter_off(B, T, H));
+    p.one_dir = top_last >= 2 ? 1 : 0;
     if (int rc = srk::gru_persistent_launch(p, true, s)) return rc;
+    if (top_last == 3) {   // the full dW_ih / dx GEMMs below read whole dgi rows: the reverse columns' true value, zero
+      const int64_t n4 = BT * 3 * H / 4;
+      hipLaunchKernelGGL(srk::zero_cols_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, dgi, BT,
+                         (int)(3 * H), (int)(3 * H), (int)(6 * H));
+      SRK_CHECK_HIP(hipGetLastError());
+    }
+    if (top_last >= 2) {
+      hipLaunchKernelGGL(srk::rev_cell_bwd_kernel, dim3((unsigned)((B * H + 255) / 256)), dim3(256), 0, s, a.gates,
+                         dy_last, B, (int)T, (int)H, dgi, dgh_edge);
+      SRK_CHECK_HIP(hipGetLastError());
+    }
   } else {
   const dim3 grid((unsigned)(2 * a.G * a.S));
   for (int step = 0; step < T; ++step) {
@@ -780,14 +944,26 @@ int srk_gru_layer_bwd_x16(const float* x, const void* x16_in, int64_t B, int64_t
   float* wpad = pad ? ws + pad_off(B, T, H, 1) : nullptr;   // [6H][in4]
   float* dwpad = pad ? wpad + 6 * H * in4 : nullptr;         // [6H][in4]
   float* dxpad = pad ? dwpad + 6 * H * in4 : nullptr;        // [BT][in4]
+  // modes 1 and 2: the reverse direction's dgi taken as its B live rows (b, T-1), lda = T 6H; mode 3 keeps the full
+  // dW_ih / dx GEMMs (their sums' order, so their bits) and drops only the reverse dW_hh
+  const bool rev_last = top_last == 1 || top_last == 2;
+  const float* dgi_rev = dgi + (T - 1) * 6 * H + 3 * H;
   {  // dW_ih_cat[6H, in] = dgi^T [6H, BT] * x [BT, in]; db_ih fused as the row sums of dgi^T
     GemmDesc g;
-    g.M = 6 * H; g.N = pad ? in4 : in; g.K = BT;
+    g.M = rev_last ? 3 * H : 6 * H; g.N = pad ? in4 : in; g.K = BT;
     g.A = dgi; g.lda = 6 * H; g.ta = true;
     g.B = pad ? ws_fwd + pad_off(B, T, H, 0) : x; g.ldb = pad ? in4 : in;   // the forward's padded x
     g.C = pad ? dwpad : dw_ih; g.ldc = pad ? in4 : in; g.beta = pad ? 0.f : beta;
     g.rowsum = db_ih; g.rowsum_beta = beta;
     if ((rc = srk::gemm_f32(g, s))) return rc;
+    if (rev_last) {   // the reverse half from its B live rows against x[:, T-1, :]
+      g.K = B;
+      g.A = dgi_rev; g.lda = T * 6 * H;
+      g.B += (T - 1) * g.ldb; g.ldb *= T;
+      g.C += 3 * H * g.ldc;
+      g.rowsum = db_ih + 3 * H;
+      if ((rc = srk::gemm_f32(g, s))) return rc;
+    }
     if (pad) {
       const int64_t n = 6 * H * in;
       hipLaunchKernelGGL(srk::unpad_cols_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dwpad, 6 * H,
@@ -810,7 +986,21 @@ int srk_gru_layer_bwd_x16(const float* x, const void* x16_in, int64_t B, int64_t
     g.batch = 2; g.sA = BT * 3 * H - 3 * H; g.sB = 3 * H; g.sC = 3 * H * H; g.sRS = 3 * H;
     // (the batched row sums exist on the ping-pong kernel only: 16-B rows, 32-bit buffer offsets)
     const bool batched = srk::g_opt_gru_dwhh_batched && srk::gemm_f32_batched_rowsum_ok(g);
-    if (g.K > 0 && batched) {
+    if (top_last) {   // the forward direction alone; dW_hh[1] = 0 and db_hh[1] = the column sums of dgh_edge[1] below
+      g.batch = 1;
+      // mode 3: the kernel and K split of the two-direction launch, so its bits for dW_hh[0]
+      g.plan_batch = (top_last == 3 && batched) ? 2 : 0;
+      if (g.K > 0) {
+        if ((rc = srk::gemm_f32(g, s))) return rc;
+      } else if (!accumulate) {
+        SRK_CHECK_HIP(hipMemsetAsync(dw_hh, 0, sizeof(float) * 3 * H * H, s));
+        SRK_CHECK_HIP(hipMemsetAsync(db_hh, 0, sizeof(float) * 3 * H, s));
+      }
+      if (!accumulate) {
+        SRK_CHECK_HIP(hipMemsetAsync(dw_hh + 3 * H * H, 0, sizeof(float) * 3 * H * H, s));
+        SRK_CHECK_HIP(hipMemsetAsync(db_hh + 3 * H, 0, sizeof(float) * 3 * H, s));
+      }
+    } else if (g.K > 0 && batched) {
       if ((rc = srk::gemm_f32(g, s))) return rc;
     } else if (g.K > 0) {
       g.batch = 1;
@@ -826,12 +1016,20 @@ int srk_gru_layer_bwd_x16(const float* x, const void* x16_in, int64_t B, int64_t
   }
   if (dx) {  // dx[BT, in] = dgi[BT, 6H] * W_ih_cat[6H, in]
     GemmDesc g;
-    g.M = BT; g.N = pad ? in4 : in; g.K = 6 * H;
+    g.M = BT; g.N = pad ? in4 : in; g.K = rev_last ? 3 * H : 6 * H;
     g.A = dgi; g.lda = 6 * H;
     if (pad && (rc = srk::pad_cols(w_ih, 6 * H, in, wpad, s))) return rc;
     g.B = pad ? wpad : w_ih; g.ldb = pad ? in4 : in;
     g.C = pad ? dxpad : dx; g.ldc = pad ? in4 : in;
     if ((rc = srk::gemm_f32(g, s))) return rc;
+    if (rev_last) {   // rows (b, T-1) += dgi_rev_last * W_ih[1]
+      g.M = B;
+      g.A = dgi_rev; g.lda = T * 6 * H;
+      g.B += 3 * H * g.ldb;
+      g.C += (T - 1) * g.ldc; g.ldc *= T;
+      g.beta = 1.f;
+      if ((rc = srk::gemm_f32(g, s))) return rc;
+    }
     if (pad) {
       const int64_t n = BT * in;
       hipLaunchKernelGGL(srk::unpad_cols_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dxpad, BT,
@@ -840,6 +1038,44 @@ int srk_gru_layer_bwd_x16(const float* x, const void* x16_in, int64_t B, int64_t
     }
   }
   return SRK_OK;
+}
+
+int srk_gru_layer_bwd_x16(const float* x, const void* x16_in, int64_t B, int64_t T, int64_t in, int64_t H,
+                          const float* w_ih, const float* w_hh, const float* y, const float* ws_fwd, const float* dy,
+                          float* dx, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, int accumulate,
+                          float* ws, void* stream) {
+  SRK_API_BEGIN
+  if (int rc = srk::check_dims(B, T, in, H)) return rc;
+  SRK_REQUIRE(x && w_ih && w_hh && y && ws_fwd && dy && dw_ih && dw_hh && db_ih && db_hh && ws, SRK_ERR_INVALID,
+              "gru_bwd: null pointer");
+  return layer_bwd(x, x16_in, B, T, in, H, w_ih, w_hh, y, ws_fwd, dy, nullptr, 0, dx, dw_ih, dw_hh, db_ih, db_hh,
+                   accumulate, ws, srk::as_stream(stream));
+  SRK_API_END
+}
+
+int srk_gru_top_last_bwd(const float* x, const void* x16_in, int64_t B, int64_t T, int64_t in, int64_t H,
+                         const float* w_ih, const float* w_hh, const float* y, const float* ws_fwd,
+                         const float* dy_last, int mode, float* dx, float* dw_ih, float* dw_hh, float* db_ih,
+                         float* db_hh, int accumulate, float* ws, void* stream) {
+  SRK_API_BEGIN
+  if (int rc = srk::check_dims(B, T, in, H)) return rc;
+  SRK_REQUIRE(x && w_ih && w_hh && y && ws_fwd && dy_last && dw_ih && dw_hh && db_ih && db_hh && ws, SRK_ERR_INVALID,
+              "gru_top_last_bwd: null pointer");
+  SRK_REQUIRE(mode >= 0 && mode <= 3, SRK_ERR_INVALID, "gru_top_last_bwd: mode must be the forward's (0 .. 3)");
+  // modes 1 .. 3 exist on the fp32 persistent path only; the forward chose the mode there
+  SRK_REQUIRE(mode == 0 || top_last_path(B, T, H), SRK_ERR_INVALID,
+              "gru_top_last_bwd: mode %d needs the fp32 persistent path its forward ran on", mode);
+  hipStream_t s = srk::as_stream(stream);
+  // the [B][T][2H] gradient the recurrence reads: zeros and the last row (what last_step's backward builds)
+  float* dy = ws + srk_gru_workspace_floats(B, T, in, H, 1);
+  const int64_t n4 = B * T * 2 * H / 4;
+  hipLaunchKernelGGL(srk::pad_last_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, dy_last, B, (int)T,
+                     (int)(2 * H), dy);
+  SRK_CHECK_HIP(hipGetLastError());
+  // mode 0 (16-bit precisions, H != 512, no persistent kernels): the full layer backward on that dy, exactly
+  // what last_step(srk_gru_layer_fwd) backpropagates
+  return layer_bwd(x, x16_in, B, T, in, H, w_ih, w_hh, y, ws_fwd, dy, dy_last, mode, dx, dw_ih, dw_hh, db_ih, db_hh,
+                   accumulate, ws, s);
   SRK_API_END
 }
 

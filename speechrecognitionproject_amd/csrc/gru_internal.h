@@ -69,7 +69,16 @@ struct GruPArgs {
   const uint16_t* y16_in;
   float* dw_part;
   int dw_mode;           // option gru_dwhh_fused bits: 2 = h_prev fetched after the exchange barrier, 4 = recurrence waves at prio 1
+  int one_dir;           // fp32 kernels: 1 = the forward direction only (0 = both).  Same grid, placement and census; the
+                         //   reverse direction's workgroups return right after place() (srk_gru_top_last_*)
 };
+
+// The GRU cell's nonlinearities, shared by the recurrence kernels and the single-cell kernels of gru.hip.
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+// 16-bit kernels and the fp32 two-chain forward (option gru_fp32_fast_cell): the hardware exp / reciprocal
+// forms (v_exp_f32, v_rcp_f32: ~1 ulp) keep the cell epilogue short on the step-to-step chain.
+__device__ __forceinline__ float sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+__device__ __forceinline__ float tanh_fast(float x) { return 2.0f * sigmoid_fast(2.0f * x) - 1.0f; }
 
 size_t fwd_lds_bytes(int H);
 size_t bwd_lds_bytes(int H);
@@ -77,6 +86,9 @@ size_t bwd_lds_bytes(int H);
 int gru_persistent_supported(int64_t B, int64_t T, int64_t H, bool backward);
 // Enqueue the whole recurrence (all T steps; batch split into co-resident chunks).
 int gru_persistent_launch(GruPArgs a, bool backward, hipStream_t s);
+// 1 if the fp32 persistent forward evaluates its cells with sigmoid_fast / tanh_fast (the two-chain kernel with
+// option gru_fp32_fast_cell), 0 if with the libm forms.
+int gru_fp32_fast_cell();
 
 // Runtime options (srk_set_option): persistent GRU recurrence on/off (default on).
 extern int g_opt_gru_persistent;
@@ -97,6 +109,10 @@ int gru_bias_part_rows(int64_t B);
 int gru_dwhh_fused_parts(int64_t B, int64_t T);
 extern int g_opt_gru_dwhh_fused;               // fused recurrent weight gradient in the 16-bit backward (default 1)
 extern int g_opt_gru_fwd_worker;               // 16-bit forward: output / input worker waves (default 0 until measured)
+// Last-step top layer (srk_gru_top_last_*, fp32 persistent path): 0 = the full layer, 1 = the backward GEMMs
+// without their all-zero reverse-direction parts, 2 = also the reverse direction as its one live cell, 3 = that cell
+// and the forward-only launches of 2 with the full dW_ih / dx GEMMs, bit for bit the full layer's results (default)
+extern int g_opt_gru_top_last;
 // Host-pinned health word (device-mapped pointer in *dev): non-zero once any persistent-kernel
 // spin-wait has given up; read without a device synchronization by srk_health_check.
 int health_word(unsigned** host, unsigned** dev);

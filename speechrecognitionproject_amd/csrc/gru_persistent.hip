@@ -53,12 +53,7 @@ constexpr unsigned kSpinLimit = 1u << 24;   // x s_sleep(2) (~128 clk) ~= 2 s at
 
 __device__ __forceinline__ v4f ld4(const float* p) { return *reinterpret_cast<const v4f*>(p); }
 __device__ __forceinline__ void st4(float* p, v4f v) { *reinterpret_cast<v4f*>(p) = v; }
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-// 16-bit kernels: the hardware exp / reciprocal forms (v_exp_f32, v_rcp_f32: ~1 ulp, far inside the
-// 16-bit operand tolerance) keep the cell epilogue short on the step-to-step chain; the fp32 kernels
-// keep the libm forms.
-__device__ __forceinline__ float sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float tanh_fast(float x) { return 2.0f * sigmoid_fast(2.0f * x) - 1.0f; }
+// (the cell nonlinearities sigmoidf_ / sigmoid_fast / tanh_fast: gru_internal.h)
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const float* base) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), (short)0, 0x7fffffff, 0x00020000);
@@ -354,6 +349,9 @@ __global__ __launch_bounds__(256, 1) void gru_fwd_persistent_kernel(GruPArgs a) 
   bool local;
   place(a, H / kUnits, dir, group, slice, local);
   trace_id(a, dir, group, slice);
+  // one_dir: this workgroup took its slot in the census; every later wait is on flags of its own (direction,
+  // group), so the reverse direction's workgroups leave here and nobody waits for them
+  if (a.one_dir && dir == 1) return;
   const int T = a.T, j0 = slice * kUnits, j = j0 + lr;
   const int b0 = a.b_begin + group * kRows;
   const int b_last = a.b_end - 1;
@@ -494,6 +492,9 @@ __global__ __launch_bounds__(256, 1) void gru_bwd_persistent_kernel(GruPArgs a) 
   bool local;
   place(a, H / kUnits, dir, group, slice, local);
   trace_id(a, dir, group, slice);
+  // one_dir: this workgroup took its slot in the census; every later wait is on flags of its own (direction,
+  // group), so the reverse direction's workgroups leave here and nobody waits for them
+  if (a.one_dir && dir == 1) return;
   const int T = a.T, B = a.B, j0 = slice * kUnits, j = j0 + lr;
   const int b0 = a.b_begin + group * kRows;
   const int b_last = a.b_end - 1;
@@ -735,6 +736,9 @@ __global__ __launch_bounds__(512, 1) void gru_fwd_persistent_dc_kernel(GruPArgs 
   bool local;
   place(a, H / kUnits, dir, group, slice, local);
   trace_id(a, dir, group, slice);
+  // one_dir: this workgroup took its slot in the census; every later wait is on flags of its own (direction,
+  // group), so the reverse direction's workgroups leave here and nobody waits for them
+  if (a.one_dir && dir == 1) return;
   const int T = a.T, j0 = slice * kUnits, j = j0 + lr;
   const int rbase = a.b_begin + group * kRows + 32 * c + 16 * rb;   // the wave's 16-row block
   const int b_last = a.b_end - 1;
@@ -945,6 +949,9 @@ __global__ __launch_bounds__(512, 1) void gru_bwd_persistent_dc_kernel(GruPArgs 
   bool local;
   place(a, S, dir, group, slice, local);
   trace_id(a, dir, group, slice);
+  // one_dir: this workgroup took its slot in the census; every later wait is on flags of its own (direction,
+  // group), so the reverse direction's workgroups leave here and nobody waits for them
+  if (a.one_dir && dir == 1) return;
   const int T = a.T, B = a.B, j0 = slice * kUnits, j = j0 + lr;
   const int rbase = a.b_begin + group * kRows + 32 * c + 16 * rb;
   const int b_last = a.b_end - 1;
@@ -2395,10 +2402,13 @@ __global__ void __launch_bounds__(256) zero_counters_kernel(unsigned* __restrict
   if (i < n) __hip_atomic_store(p + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+int gru_fp32_fast_cell() { return g_opt_gru_fast_cell && g_opt_gru_dc && dc_occupancy_ok<512>() > 0; }
+
 int gru_persistent_launch(GruPArgs a, bool backward, hipStream_t s) {
   const int gmax = gru_persistent_groups(a.H);
   SRK_REQUIRE(gmax > 0 && a.H == 512, SRK_ERR_INVALID, "gru persistent: unsupported H");
   const int prec = matmul_prec();
+  SRK_REQUIRE(!a.one_dir || prec == kPrecF32, SRK_ERR_INVALID, "gru persistent: one_dir is an fp32 mode");
   const bool wide = lp2_wide(a.B, prec, backward, a.x_in ? a.in : 0) && (!backward || a.dgi16 != nullptr);
   const int rows_per_launch = wide ? 512 : gmax * kRows;
   // 16-bit operands: the 32 x 32 workgroup kernels (the backward one writes the 16-bit outputs only)
@@ -2432,7 +2442,7 @@ int gru_persistent_launch(GruPArgs a, bool backward, hipStream_t s) {
     hipLaunchKernelGGL(zero_counters_kernel, dim3((kCounterFloats + 255) / 256), dim3(256), 0, s, ac.counters,
                        (int)kCounterFloats);
     const dim3 grid((unsigned)(2 * ac.G * slices));
-    const double flops = 2.0 * 2.0 * (double)(ac.b_end - c0) * 3 * a.H * a.H * (a.T - 1);
+    const double flops = 2.0 * (a.one_dir ? 1.0 : 2.0) * (double)(ac.b_end - c0) * 3 * a.H * a.H * (a.T - 1);
     ProfScope prof(backward ? (prec == kPrecF32 ? "gru_bwd_seq" : "gru_bwd_seq_lp")
                             : (prec == kPrecF32 ? "gru_fwd_seq" : "gru_fwd_seq_lp"), s, flops);
     prof.detail("gru_%s_persistent%s_kernel B%d T%d chunk%d", backward ? "bwd" : "fwd",

@@ -54,6 +54,7 @@ int g_opt_gru_dc_prio = 0;
 int g_opt_gru_dwhh_fused = 1;
 int g_opt_gru_fwd_worker = 0;
 int g_opt_gru_dwhh_batched = 1;
+int g_opt_gru_top_last = 3;
 int g_opt_gemm_skinny = 1;
 int g_opt_attn_pool_regs = 1;
 std::atomic<int64_t> g_scratch_gen{0};
@@ -524,6 +525,13 @@ int srk_set_option(const char* name, int64_t value) {
   }
   if (n == "gru_dwhh_batched") {   // 16-bit GRU backward: both directions' dW_hh in one batched GEMM (1) or two (0)
     srk::g_opt_gru_dwhh_batched = value != 0;
+    return SRK_OK;
+  }
+  if (n == "gru_top_last") {   // srk_gru_top_last_* on the fp32 persistent path: 0 the full layer, 1 the backward GEMMs
+                               // pruned, 2 also the reverse direction as one cell, 3 that cell with the full dW_ih /
+                               // dx GEMMs: the full layer's bits (default)
+    SRK_REQUIRE(value >= 0 && value <= 3, SRK_ERR_INVALID, "gru_top_last must be 0 .. 3");
+    srk::g_opt_gru_top_last = (int)value;
     return SRK_OK;
   }
   if (n == "gru_lp_32x32") {   // 16-bit recurrence: 32 x 32 workgroups (1) or 64 rows x 16 units (0)

@@ -12,7 +12,7 @@ BatchNorm under data parallelism uses per-rank batch statistics (DESIGN.md §Mul
 import torch
 import torch.nn as nn
 
-from ..nn import BatchNorm1d, BiGRU, Conv1d, Linear, last_step
+from ..nn import BatchNorm1d, BiGRU, Conv1d, Linear
 from ._common import DEVICE, accuracy, class_accuracy   # noqa: F401
 
 
@@ -46,8 +46,7 @@ class GRU(nn.Module):
         self.fc2 = Linear(512 * 2, 12)
 
     def forward(self, x):
-        x, _ = self.gru(x)
-        return self.fc2(last_step(x))
+        return self.fc2(self.gru.forward_last(x))
 
 
 class Network(nn.Module):

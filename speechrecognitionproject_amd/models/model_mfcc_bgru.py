@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from .. import features
-from ..nn import BiGRU, Linear, last_step
+from ..nn import BiGRU, Linear
 from ._common import DEVICE, accuracy, class_accuracy   # noqa: F401  (plugin API)
 
 
@@ -40,5 +40,4 @@ class Network(nn.Module):
                 inx = features.mfcc(x, time_major=True)     # [B, 51, 39] = transpose(mfcc, 1, 2)
             else:
                 inx = features.mfcc40x98(x)                 # [B, 98, 40] (perf-only variant)
-        inx, _ = self.gru(inx)
-        return self.fc(last_step(inx))
+        return self.fc(self.gru.forward_last(inx))

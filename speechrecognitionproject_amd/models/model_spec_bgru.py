@@ -5,7 +5,7 @@ import torch
 import torch.nn as nn
 
 from .. import features
-from ..nn import BiGRU, Linear, last_step
+from ..nn import BiGRU, Linear
 from ._common import DEVICE, accuracy, class_accuracy   # noqa: F401
 
 
@@ -23,5 +23,4 @@ class Network(nn.Module):
     def forward(self, x):
         with torch.no_grad():
             inx = features.spec(x, transposed=True)     # [B, 49, 321] = transpose(spec, 1, 2)
-        inx, _ = self.gru(inx)
-        return self.fc(last_step(inx))
+        return self.fc(self.gru.forward_last(inx))

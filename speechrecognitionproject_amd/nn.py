@@ -143,6 +143,70 @@ class _GRULayerFn(torch.autograd.Function):
         return (dx, None, dw_ih[0], dw_ih[1], dw_hh[0], dw_hh[1], db_ih[0], db_ih[1], db_hh[0], db_hh[1])
 
 
+class _GRUTopLastFn(torch.autograd.Function):
+    """The top BiGRU layer of a model that reads only the last step (srk_gru_top_last_fwd / _bwd): returns row T-1
+    of the layer, [B, 2H], and takes dy_last [B, 2H] in backward.  Everything around the kernels is _GRULayerFn's:
+    grad_on, the in-place accumulation into FlatParams grads, the reducer hand-shake, the backward at its forward's
+    precision.  The full y is kept for the backward only and never returned (in the library's modes 2 and 3 its
+    reverse half is unwritten below the last step)."""
+
+    @staticmethod
+    def forward(ctx, x, grad_on, w_ih_f, w_ih_r, w_hh_f, w_hh_r, b_ih_f, b_ih_r, b_hh_f, b_hh_r):
+        B, T, IN = x.shape
+        H = w_hh_f.shape[-1]
+        x = x.contiguous()
+        w_ih, w_hh = _dir_pair(w_ih_f, w_ih_r), _dir_pair(w_hh_f, w_hh_r)
+        b_ih, b_hh = _dir_pair(b_ih_f, b_ih_r), _dir_pair(b_hh_f, b_hh_r)
+        _check_cuda(x, w_ih, w_hh, b_ih, b_hh)
+        y = torch.empty((B, T, 2 * H), device=x.device, dtype=torch.float32)
+        y_last = torch.empty((B, 2 * H), device=x.device, dtype=torch.float32)
+        ws = torch.empty(int(_lib.lib().srk_gru_top_last_workspace_floats(B, T, IN, H, 0)), device=x.device)
+        x16 = _copy16_get(x) if IN % 8 == 0 else None   # the layer below's 16-bit copy of its h (16-bit modes)
+        mode = ctypes.c_int(0)
+        call("srk_gru_top_last_fwd", ptr(x), _optr(x16), B, T, IN, H, ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh),
+             ptr(y), ptr(y_last), ptr(ws), ctypes.byref(mode), stream_ptr())
+        ctx.x16 = x16
+        ctx.mode = mode.value
+        ctx.save_for_backward(x, w_ih, w_hh, y, ws)
+        ctx.dims = (B, T, IN, H)
+        ctx.params = (w_ih_f, w_ih_r, w_hh_f, w_hh_r, b_ih_f, b_ih_r, b_hh_f, b_hh_r)
+        ctx.prec = _lib.matmul_precision()
+        red = _reducer_of(w_ih_f)
+        if red is not None and grad_on and any(ctx.needs_input_grad):
+            red.persistent_pending(1)
+        return y_last
+
+    @staticmethod
+    def backward(ctx, dy_last):
+        x, w_ih, w_hh, y, ws = ctx.saved_tensors
+        B, T, IN, H = ctx.dims
+        P = ctx.params
+        dy_last = dy_last.contiguous()
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        targets = [_grad_pair(P[2 * i], P[2 * i + 1]) for i in range(4)]
+        acc = all(t is not None for t in targets) and all(ctx.needs_input_grad[2:])
+        if acc:
+            dw_ih, dw_hh, db_ih, db_hh = targets
+        else:
+            dw_ih, dw_hh = torch.empty_like(w_ih), torch.empty_like(w_hh)
+            db_ih = torch.empty((2, 3 * H), device=x.device)
+            db_hh = torch.empty((2, 3 * H), device=x.device)
+        ws2 = torch.empty(int(_lib.lib().srk_gru_top_last_workspace_floats(B, T, IN, H, 1)), device=x.device)
+        x16, ctx.x16 = ctx.x16, None
+        with _lib.precision_scope(ctx.prec):
+            call("srk_gru_top_last_bwd", ptr(x), _optr(x16), B, T, IN, H, ptr(w_ih), ptr(w_hh), ptr(y), ptr(ws),
+                 ptr(dy_last), ctx.mode, _optr(dx), ptr(dw_ih), ptr(dw_hh), ptr(db_ih), ptr(db_hh), int(acc), ptr(ws2),
+                 stream_ptr())
+        red = _reducer_of(P[0])
+        if red is not None:
+            red.persistent_done()
+            if acc:
+                red.mark_ready(P)
+        if acc:
+            return (dx, None) + (None,) * 8
+        return (dx, None, dw_ih[0], dw_ih[1], dw_hh[0], dw_hh[1], db_ih[0], db_ih[1], db_hh[0], db_hh[1])
+
+
 class BiGRU(tnn.Module):
     """Drop-in for ``nn.GRU(input_size, hidden_size, num_layers, bidirectional=True,
     batch_first=True)`` (h0 = 0, no inter-layer dropout).  ``forward(x) -> (output, h_n)``."""
@@ -178,6 +242,15 @@ class BiGRU(tnn.Module):
             H = self.hidden_size
             finals += [h[:, -1, :H], h[:, 0, H:]]
         return h, torch.stack(finals)
+
+    def forward_last(self, x):
+        """``forward(x)[0][:, -1, :]`` -> [B, 2H] for the models that read nothing else (fc on the last step):
+        the top layer computes only what that row needs (_GRUTopLastFn); no h_n is built."""
+        require_gpu()
+        h = x
+        for layer in range(self.num_layers - 1):
+            h = _GRULayerFn.apply(h, torch.is_grad_enabled(), *self._pairs(layer))
+        return _GRUTopLastFn.apply(h, torch.is_grad_enabled(), *self._pairs(self.num_layers - 1))
 
 
 class _LastStepFn(torch.autograd.Function):
