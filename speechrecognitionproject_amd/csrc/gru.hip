@@ -12,9 +12,16 @@
 //            then the gate derivatives as epilogue), followed by the weight-gradient GEMMs
 //            (dW_ih = dgi^T x, dW_hh = dgh^T h_prev with K = B*T) and column sums for the biases.
 //
-// Workspace (fp32, caller-owned; sizes in srk_gru_workspace_floats):
+// On H = 512 the T step launches are ONE launch per batch chunk of a persistent recurrence kernel
+// (gru_persistent.hip; gru_rec_plan picks the variant), and in bf16 / fp16 mode the GEMM operands live in memory
+// in 16 bit.
+//
+// Workspace (fp32, caller-owned; sizes in srk_gru_workspace_floats; struct GruWs below is the layout):
 //   fwd:  gi [B*T, 6H] | gates [2][T][B][4H] (r, z, n, W_hn h + b_hn)       — kept for backward
 //   bwd:  dgi [B*T, 6H] | dgh [2][B][T][3H] | dgh_edge [2][B][3H] | dhz [2][B][H]
+//   both, each block 64-float aligned: | the persistent kernels' hand-off ring | their kCounterFloats step-ordering
+//   words | the in4 pad block (in % 4 != 0) | the 16-bit block (H = 512: x16, W16, y16 / bias partials, dW_ih
+//   and dx at width in8); srk_gru_top_last_bwd appends its [B][T][2H] dy.
 #include <algorithm>
 #include <mutex>
 
@@ -433,25 +440,20 @@ __global__ void to16_vec8_kernel(const float* __restrict__ src, int64_t n8, uint
   *reinterpret_cast<u4*>(dst + 8 * i) = __builtin_bit_cast(u4, h);
 }
 
-int to16(const float* src, int64_t rows, int64_t cols, uint16_t* dst, int64_t colsp, hipStream_t s) {
-  const int64_t n = rows * colsp;
-  if (cols == colsp && n % 8 == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0) {
-    const int64_t n8 = n / 8;
-    if (matmul_prec() == kPrecF16)
-      hipLaunchKernelGGL(to16_vec8_kernel<true>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, src, n8, dst);
-    else
-      hipLaunchKernelGGL(to16_vec8_kernel<false>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, src, n8, dst);
-    SRK_CHECK_HIP(hipGetLastError());
-    return SRK_OK;
-  }
-  if (matmul_prec() == kPrecF16)
-    hipLaunchKernelGGL(to16_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, rows, (int)cols,
-                       dst, (int)colsp);
-  else
-    hipLaunchKernelGGL(to16_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, rows, (int)cols,
-                       dst, (int)colsp);
+// The launch of this file's elementwise kernels: one thread per element (or vector) of n, 256-thread blocks.
+template <class... P, class... A>
+int launch256(void (*kernel)(P...), int64_t n, hipStream_t s, A... args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, static_cast<P>(args)...);
   SRK_CHECK_HIP(hipGetLastError());
   return SRK_OK;
+}
+
+int to16(const float* src, int64_t rows, int64_t cols, uint16_t* dst, int64_t colsp, hipStream_t s) {
+  const int64_t n = rows * colsp;
+  const bool f16 = matmul_prec() == kPrecF16;
+  if (cols == colsp && n % 8 == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0)
+    return launch256(f16 ? to16_vec8_kernel<true> : to16_vec8_kernel<false>, n / 8, s, src, n / 8, dst);
+  return launch256(f16 ? to16_kernel<true> : to16_kernel<false>, n, s, src, rows, cols, dst, colsp);
 }
 // Bias gradients from the 16-bit backward kernel's partials [part][2 dir][4][H] (sums of dar, daz,
 // dan, dan * r), summed over the valid (chunk, group) parts in order: db_ih = (dar, daz, dan),
@@ -530,11 +532,7 @@ int gru_scratch(size_t floats, float** out) {
 inline int64_t pad4(int64_t v) { return (v + 3) / 4 * 4; }
 inline bool padded_in(int64_t in) { return in % 4 != 0; }
 int pad_cols(const float* src, int64_t rows, int64_t cols, float* dst, hipStream_t s) {
-  const int64_t n = rows * pad4(cols);
-  hipLaunchKernelGGL(pad_cols_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, rows, (int)cols, dst,
-                     (int)pad4(cols));
-  SRK_CHECK_HIP(hipGetLastError());
-  return SRK_OK;
+  return launch256(pad_cols_kernel, rows * pad4(cols), s, src, rows, cols, dst, pad4(cols));
 }
 
 }  // namespace
@@ -554,62 +552,135 @@ int release_gru_scratch() {
 
 using srk::GemmDesc;
 
+namespace {
+
+int64_t up64(int64_t v) { return (v + 63) / 64 * 64; }
+int64_t in8_of(int64_t in) { return (in + 7) / 8 * 8; }
+
+// THE layout of a layer's forward or backward workspace: every member's offset in floats, built once per call.
+// Blocks start 64-float aligned; the backward finds the forward's saved members with the forward's GruWs.
+struct GruWs {
+  // forward: gi [B*T][6H] | gates [2][T][B][4H] (r, z, n, W_hn h + b_hn; kept for the backward)
+  int64_t gi = 0, gates = 0;
+  // backward: dgi [B*T][6H] | dgh [2][B][T][3H] | dgh_edge [2][B][3H] | dhz [2][B][H]; on the 16-bit path dgi16
+  // [B*T][6H] (at dgi) and dgh16 [2][B][T][3H] alias the fp32 dgi region, unused in that mode
+  int64_t dgi = 0, dgh = 0, dgh_edge = 0, dhz = 0, dgh16 = 0;
+  // the persistent kernels' hand-off ring in MFMA-fragment order (fwd: h [2 dir][kHandoffSlots][rows][H], bwd: dg
+  // [2 dir][kHandoffSlots][rows][3H]; rows = the 64-row groups of one launch chunk: <= 512, or B rounded up to 64),
+  // then their kCounterFloats step-ordering words (gru_persistent.hip)
+  int64_t xbuf = 0, counters = 0;
+  // for an input width that is no multiple of 4 (srk::padded_in), at width in4:
+  //   fwd: x padded [B*T][in4] (kept for the backward's dW_ih) | W_ih padded [6H][in4]
+  //   bwd: W_ih padded [6H][in4] | dW_ih padded [6H][in4] | dx padded [B*T][in4]
+  int64_t xpad = 0, wpad = 0, dwpad = 0, dxpad = 0;
+  // H == 512, the block of the 16-bit path (GruPath::h16), at width in8:
+  //   fwd: x16 [B*T][in8] | W_ih16 [6H][in8] | y16 [B*T][2H]       (16-bit elements, kept for the backward)
+  //   bwd: bias partials [8 * chunks][2][4][H] | dW_ih [6H][in8] | dx [B*T][in8]   (fp32; the last two are only
+  //        there when in8 != in)
+  int64_t x16 = 0, w16 = 0, y16 = 0;
+  int64_t part = 0, dwpad8 = 0, dxpad8 = 0;
+  int64_t total = 0;       // srk_gru_workspace_floats
+  int64_t dy = 0;          // srk_gru_top_last_bwd: the [B][T][2H] gradient behind the layer's workspace
+  int64_t top_total = 0;   // srk_gru_top_last_workspace_floats
+};
+
+GruWs gru_ws(int64_t B, int64_t T, int64_t in, int64_t H, bool backward) {
+  GruWs w;
+  const int64_t BT = B * T, in4 = srk::pad4(in), in8 = in8_of(in);
+  const int64_t ring = srk::kHandoffSlots * std::min<int64_t>(up64(B), 512) * H;
+  if (!backward) {
+    w.gates = BT * 6 * H;
+    w.xbuf = up64(w.gates + 2 * T * B * 4 * H);
+    w.counters = w.xbuf + 2 * ring;
+  } else {
+    w.dgh = BT * 6 * H;
+    w.dgh16 = BT * 6 * H / 2;
+    w.dgh_edge = w.dgh + 2 * BT * 3 * H;
+    w.dhz = w.dgh_edge + 2 * B * 3 * H;
+    w.xbuf = up64(w.dhz + 2 * B * H);
+    w.counters = w.xbuf + 6 * ring;
+  }
+  const int64_t pad = up64(w.counters + srk::kCounterFloats);
+  int64_t e = pad + 64;
+  if (srk::padded_in(in)) {
+    if (!backward) {
+      w.xpad = pad;
+      w.wpad = w.xpad + BT * in4;
+    } else {
+      w.wpad = pad;
+      w.dwpad = w.wpad + 6 * H * in4;
+      w.dxpad = w.dwpad + 6 * H * in4;
+    }
+    e += BT * in4 + (backward ? 2 : 1) * 6 * H * in4 + 64;
+  }
+  w.total = e = up64(e);
+  if (H == 512 && !backward) {
+    w.x16 = e;
+    w.w16 = w.x16 + up64(BT * in8 / 2 + 1);
+    w.y16 = w.w16 + up64(6 * H * in8 / 2 + 1);
+    w.total = w.y16 + up64(BT * 2 * H / 2 + 1) + 64;
+  } else if (H == 512) {
+    w.part = e;
+    w.dwpad8 = w.part + up64((B + 255) / 256 * 8 * 2 * 4 * H);   // <= 8 partials per 256-row chunk
+    w.dxpad8 = w.dwpad8 + up64(6 * H * in8);
+    w.total = (in8 != in ? w.dxpad8 + up64(BT * in8) : w.dwpad8) + 64;
+  }
+  w.dy = w.total;
+  w.top_total = w.total + (backward ? up64(BT * 2 * H) : 0);
+  return w;
+}
+
+// How one entry-point call runs its layer, decided once: the recurrence plan of each direction of travel and the
+// path they put the layer on.
+struct GruPath {
+  srk::GruRecPlan fwd, bwd;
+  // both directions of travel on the persistent kernels, or neither (they hand the saved gates over
+  // unit-interleaved, the per-step kernels in the plain layout)
+  bool persistent = false;
+  // the 16-bit path: a 16-bit precision, the persistent kernels, and 32-bit byte offsets for the 16-bit operands
+  // in memory (x16 / W16 / y16, dgi16 / dgh16); every GEMM of the layer reads those
+  bool h16 = false;
+  // srk_gru_top_last_*: modes 1 .. 3 (option gru_top_last) exist on the fp32 persistent path only (top_last_ok);
+  // everywhere else 0 = the full layer, exactly what srk_gru_layer_* compute
+  bool top_last_ok = false;
+  int top_last = 0;
+};
+
+GruPath gru_path(int64_t B, int64_t T, int64_t in, int64_t H) {
+  GruPath p;
+  const int prec = srk::matmul_prec();
+  const srk::GruOpts o = srk::gru_opts();
+  const bool out16 = prec != srk::kPrecF32 && (double)B * T * 6 * H * 2 < 2147483647.0 &&
+                     (double)B * T * in8_of(in) * 2 < 2147483647.0;
+  // (a persistent forward projects an input of in <= kFusedIn itself)
+  p.fwd = srk::gru_rec_plan(B, T, H, in <= srk::kFusedIn ? (int)in : 0, prec, false, out16, o, srk::gru_fit_measured);
+  p.bwd = srk::gru_rec_plan(B, T, H, 0, prec, true, out16, o, srk::gru_fit_measured);
+  p.persistent = p.fwd.variant != srk::kGruStep && p.bwd.variant != srk::kGruStep;
+  p.h16 = p.persistent && out16;
+  p.top_last_ok = prec == srk::kPrecF32 && H == 512 && p.persistent;
+  p.top_last = p.top_last_ok ? srk::g_opt_gru_top_last : 0;
+  return p;
+}
+
+// The GruPArgs fields every persistent launch of a layer sets: dims, recurrent weights, hand-off ring, counters.
+srk::GruPArgs rec_args(int64_t B, int64_t T, int64_t H, const float* w_hh, float* ws, const GruWs& L) {
+  srk::GruPArgs p{};
+  p.B = (int)B; p.T = (int)T; p.H = (int)H;
+  p.w_hh = w_hh;
+  p.xbuf = ws + L.xbuf;
+  p.counters = reinterpret_cast<unsigned*>(ws + L.counters);
+  return p;
+}
+
+inline uint16_t* u16(float* p) { return reinterpret_cast<uint16_t*>(p); }
+inline const uint16_t* u16(const float* p) { return reinterpret_cast<const uint16_t*>(p); }
+
+}  // namespace
+
 extern "C" {
 
-// Both workspaces end with a 64-float-aligned block of kCounterFloats arrival counters (the
-// persistent recurrence kernels' step ordering; see gru_persistent.hip).
-// Before them, 64-float aligned, the persistent kernels' hand-off ring in MFMA-fragment order
-// (fwd: h [2 dir][kHandoffSlots][rows][H], bwd: dg [2 dir][kHandoffSlots][rows][3H]).
-static int64_t fwd_xbuf_off(int64_t B, int64_t T, int64_t H) { return (B * T * 6 * H + 2 * T * B * 4 * H + 63) / 64 * 64; }
-static int64_t bwd_xbuf_off(int64_t B, int64_t T, int64_t H) {
-  return (B * T * 6 * H + 2 * B * T * 3 * H + 2 * B * 3 * H + 2 * B * H + 63) / 64 * 64;
-}
-// (rows padded to the 64-row groups of one launch chunk: <= 512 rows, or B rounded up to 64)
-static int64_t xbuf_rows(int64_t B) { return std::min<int64_t>((B + 63) / 64 * 64, 512); }
-static int64_t fwd_counter_off(int64_t B, int64_t T, int64_t H) {
-  return fwd_xbuf_off(B, T, H) + 2 * srk::kHandoffSlots * xbuf_rows(B) * H;
-}
-static int64_t bwd_counter_off(int64_t B, int64_t T, int64_t H) {
-  return bwd_xbuf_off(B, T, H) + 6 * srk::kHandoffSlots * xbuf_rows(B) * H;
-}
-
-// After the counters, for an input width that is not a multiple of 4 (srk::padded_in):
-//   fwd: x padded [B*T][in4] (kept for the backward's dW_ih) | W_ih padded [6H][in4]
-//   bwd: W_ih padded [6H][in4] | dW_ih padded [6H][in4] | dx padded [B*T][in4]
-static int64_t pad_off(int64_t B, int64_t T, int64_t H, int backward) {
-  return ((backward ? bwd_counter_off(B, T, H) : fwd_counter_off(B, T, H)) + srk::kCounterFloats + 63) / 64 * 64;
-}
-
-// Then the bf16 / fp16 ("h16") region, used when the 16-bit persistent kernels run (use_h16):
-//   fwd: x16 [B*T][in8] | W_ih16 [6H][in8] | y16 [B*T][2H]          (16-bit, kept for the backward)
-//   bwd: bias partials [8 * chunks][2][4][H] | dW_ih [6H][in8] | dx [B*T][in8]   (fp32; the last two
-//        only when in8 != in); dgi16 / dgh16 alias the fp32 dgi region (unused in this mode).
-static int64_t pad_end(int64_t B, int64_t T, int64_t in, int64_t H, int backward) {
-  int64_t e = pad_off(B, T, H, backward) + 64;
-  if (srk::padded_in(in)) {
-    const int64_t in4 = srk::pad4(in);
-    e += (backward ? 2 * 6 * H * in4 + B * T * in4 : B * T * in4 + 6 * H * in4) + 64;
-  }
-  return (e + 63) / 64 * 64;
-}
-static int64_t up64(int64_t v) { return (v + 63) / 64 * 64; }
-static int64_t in8_of(int64_t in) { return (in + 7) / 8 * 8; }
-static int64_t h16_floats(int64_t B, int64_t T, int64_t in, int64_t H, int backward) {
-  const int64_t in8 = in8_of(in), BT = B * T;
-  if (!backward) return up64(BT * in8 / 2 + 1) + up64(6 * H * in8 / 2 + 1) + up64(BT * 2 * H / 2 + 1);
-  const int64_t chunks = (B + 255) / 256;
-  return up64(chunks * 8 * 2 * 4 * H) + (in8 != in ? up64(6 * H * in8) + up64(BT * in8) : 0);   // <= 8 parts per chunk
-}
-// The 16-bit path: a 16-bit precision, the persistent kernels (both directions of the layer), and
-// 32-bit byte offsets for the 16-bit GEMM operands.
-static bool use_h16(int64_t B, int64_t T, int64_t in, int64_t H) {
-  return srk::matmul_prec() != srk::kPrecF32 && srk::g_opt_gru_persistent &&
-         srk::gru_persistent_supported(B, T, H, false) && srk::gru_persistent_supported(B, T, H, true) &&
-         (double)B * T * 6 * H * 2 < 2147483647.0 && (double)B * T * in8_of(in) * 2 < 2147483647.0;
-}
-
 int64_t srk_gru_workspace_floats(int64_t B, int64_t T, int64_t in, int64_t H, int backward) {
-  return pad_end(B, T, in, H, backward) + (H == 512 ? h16_floats(B, T, in, H, backward) + 64 : 0);
+  return gru_ws(B, T, in, H, backward != 0).total;
 }
 
 int srk_gru_layer_fwd(const float* x, int64_t B, int64_t T, int64_t in, int64_t H, const float* w_ih,
@@ -618,44 +689,35 @@ int srk_gru_layer_fwd(const float* x, int64_t B, int64_t T, int64_t in, int64_t 
 }
 
 int64_t srk_gru_y16_offset(int64_t B, int64_t T, int64_t in, int64_t H) {
-  if (srk::check_dims(B, T, in, H) || H != 512 || !use_h16(B, T, in, H)) return -1;
-  const int64_t in8 = in8_of(in), BT = B * T;
-  return pad_end(B, T, in, H, 0) + up64(BT * in8 / 2 + 1) + up64(6 * H * in8 / 2 + 1);
+  if (srk::check_dims(B, T, in, H) || H != 512 || !gru_path(B, T, in, H).h16) return -1;
+  return gru_ws(B, T, in, H, false).y16;
 }
 
-// The fp32 persistent path of this layer: both directions' recurrences on the persistent kernels (or neither: they
-// hand the saved gates over unit-interleaved, the per-step kernels in the plain layout).
-static bool persistent_pair(int64_t B, int64_t T, int64_t H) {
-  return srk::g_opt_gru_persistent && srk::gru_persistent_supported(B, T, H, false) &&
-         srk::gru_persistent_supported(B, T, H, true);
-}
-// How srk_gru_top_last_* run a layer (option gru_top_last): modes 1 .. 3 on the fp32 persistent path only (H = 512);
-// everywhere else 0 = the full layer, exactly what srk_gru_layer_* compute.
-static bool top_last_path(int64_t B, int64_t T, int64_t H) {
-  return srk::matmul_prec() == srk::kPrecF32 && H == 512 && persistent_pair(B, T, H);
-}
-static int top_last_mode(int64_t B, int64_t T, int64_t H) { return top_last_path(B, T, H) ? srk::g_opt_gru_top_last : 0; }
-
-// One layer forward.  top_last >= 2 (top_last_mode, with y_last): only row T-1 of y is used, so the reverse direction
-// is its one cell at t = T-1 (rev_cell_fwd_kernel) and its rows t < T-1 of gi / y / the gates are never written.
+// One layer forward.  top_last >= 2 (GruPath::top_last, with y_last): only row T-1 of y is used, so the reverse
+// direction is its one cell at t = T-1 (rev_cell_fwd_kernel) and its rows t < T-1 of gi / y / the gates are never
+// written.
 static int layer_fwd(const float* x, const void* x16_in, int64_t B, int64_t T, int64_t in, int64_t H,
                      const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* y,
-                     float* ws, int top_last, float* y_last, hipStream_t s) {
+                     float* ws, const GruPath& path, int top_last, float* y_last, hipStream_t s) {
   const bool rev_cell = top_last >= 2;
-  float* gi = ws;
-  float* gates = ws + B * T * 6 * H;
+  SRK_REQUIRE(!rev_cell || (path.persistent && !path.h16 && y_last), SRK_ERR_INTERNAL,
+              "gru_fwd: rev_cell off the fp32 persistent path");
+  const GruWs L = gru_ws(B, T, in, H, false);
+  const int64_t BT = B * T;
+  float* gi = ws + L.gi;
+  float* gates = ws + L.gates;
   uint16_t* y16 = nullptr;
-  if (use_h16(B, T, in, H)) {   // 16-bit operands in memory: x, W_ih rounded once, h written by the kernel
-    const int64_t in8 = in8_of(in), BT = B * T;
-    uint16_t* x16 = reinterpret_cast<uint16_t*>(ws + pad_end(B, T, in, H, 0));
-    uint16_t* w16 = x16 + 2 * up64(BT * in8 / 2 + 1);
-    y16 = w16 + 2 * up64(6 * H * in8 / 2 + 1);
+  const bool fuse = path.persistent && in <= srk::kFusedIn;   // the kernel projects the input itself (no gi GEMM)
+  if (path.h16) {   // 16-bit operands in memory: x, W_ih rounded once, h written by the kernel
+    const int64_t in8 = in8_of(in);
+    uint16_t* x16 = u16(ws + L.x16);
+    uint16_t* w16 = u16(ws + L.w16);
+    y16 = u16(ws + L.y16);
     // x16_in: the producer's copy of x (the previous layer's y16), used as it is: in == in8 only
     SRK_REQUIRE(!x16_in || (in8 == in && reinterpret_cast<uintptr_t>(x16_in) % 16 == 0), SRK_ERR_INVALID,
                 "gru_fwd: a ready 16-bit x needs in % 8 == 0 and 16-B alignment");
     if (x16_in) x16 = const_cast<uint16_t*>(static_cast<const uint16_t*>(x16_in));
     else if (int rc = srk::to16(x, BT, in, x16, in8, s)) return rc;
-    const bool fuse = in <= srk::kFusedIn;   // the kernel projects the input itself (no gi GEMM)
     // W16: the gi GEMM's operand; with the fused projection only the backward's dx needs it (rounded there)
     if (!fuse) {
       if (int rc = srk::to16(w_ih, 6 * H, in, w16, in8, s)) return rc;
@@ -667,69 +729,47 @@ static int layer_fwd(const float* x, const void* x16_in, int64_t B, int64_t T, i
       g.bias = b_ih; g.bias_mode = 1;
       if (int rc = srk::gemm_f32(g, s)) return rc;
     }
-    srk::GruPArgs p{};
-    p.B = (int)B; p.T = (int)T; p.H = (int)H;
-    p.gi = gi; p.w_hh = w_hh; p.b_hh = b_hh; p.y = y; p.gates = gates; p.y16 = y16;
-    if (fuse) { p.x_in = x; p.w_ih = w_ih; p.b_ih = b_ih; p.in = (int)in; }
-    p.xbuf = ws + fwd_xbuf_off(B, T, H);
-    p.counters = reinterpret_cast<unsigned*>(ws + fwd_counter_off(B, T, H));
-    return srk::gru_persistent_launch(p, false, s);
-  }
-  const float* xa = x;
-  const float* wa = w_ih;
-  int64_t ink = in;
-  if (srk::padded_in(in)) {   // zero-pad the input width to a multiple of 4 (vector GEMM paths)
-    ink = srk::pad4(in);
-    float* xp = ws + pad_off(B, T, H, 0);
-    float* wp = xp + B * T * ink;
-    if (int rc = srk::pad_cols(x, B * T, in, xp, s)) return rc;
-    if (int rc = srk::pad_cols(w_ih, 6 * H, in, wp, s)) return rc;
-    xa = xp;
-    wa = wp;
-  }
-  const bool persistent = persistent_pair(B, T, H);
-  SRK_REQUIRE(!rev_cell || (persistent && y_last), SRK_ERR_INTERNAL, "gru_fwd: rev_cell off the persistent path");
-  const bool fuse = persistent && in <= srk::kFusedIn;   // the kernel projects the input itself
-  if (!fuse) {
-    // gi[B*T, 6H] = x[B*T, in] * W_ih_cat[6H, in]^T + b_ih_cat (rev_cell: the forward direction's 3H columns)
-    GemmDesc g;
-    g.M = B * T; g.N = rev_cell ? 3 * H : 6 * H; g.K = ink;
-    g.A = xa; g.lda = ink;
-    g.B = wa; g.ldb = ink; g.tb = true;
-    g.C = gi; g.ldc = 6 * H;
-    g.bias = b_ih; g.bias_mode = 1;
-    if (int rc = srk::gemm_f32(g, s)) return rc;
-  }
-  if (rev_cell) {
-    // gi[(b, T-1)][3H:6H] = x[b, T-1, :] * W_ih[1]^T + b_ih[1]: B strided rows, where the full GEMM puts them
-    GemmDesc g;
-    g.M = B; g.N = 3 * H; g.K = ink;
-    g.A = xa + (T - 1) * ink; g.lda = T * ink;
-    g.B = wa + 3 * H * ink; g.ldb = ink; g.tb = true;
-    g.C = gi + (T - 1) * 6 * H + 3 * H; g.ldc = T * 6 * H;
-    g.bias = b_ih + 3 * H; g.bias_mode = 1;
-    g.no_split = top_last == 3;   // mode 3: the full projection's sum order (wherever that GEMM runs unsplit)
-    if (int rc = srk::gemm_f32(g, s)) return rc;
-  }
-  if (persistent) {
-    srk::GruPArgs p{};
-    p.B = (int)B; p.T = (int)T; p.H = (int)H;
-    p.gi = gi; p.w_hh = w_hh; p.b_hh = b_hh; p.y = y; p.gates = gates;
-    if (fuse) { p.x_in = x; p.w_ih = w_ih; p.b_ih = b_ih; p.in = (int)in; }
-    p.xbuf = ws + fwd_xbuf_off(B, T, H);
-    p.counters = reinterpret_cast<unsigned*>(ws + fwd_counter_off(B, T, H));
-    p.one_dir = rev_cell ? 1 : 0;
-    if (int rc = srk::gru_persistent_launch(p, false, s)) return rc;
-    if (rev_cell) {   // after the recurrence: y_last's forward half is its last step
-      const dim3 grid((unsigned)((B * H + 255) / 256));
-      if (srk::gru_fp32_fast_cell())
-        hipLaunchKernelGGL(srk::rev_cell_fwd_kernel<true>, grid, dim3(256), 0, s, gi, b_hh, B, (int)T, (int)H, y,
-                           y_last, gates);
-      else
-        hipLaunchKernelGGL(srk::rev_cell_fwd_kernel<false>, grid, dim3(256), 0, s, gi, b_hh, B, (int)T, (int)H, y,
-                           y_last, gates);
-      SRK_CHECK_HIP(hipGetLastError());
+  } else {
+    const float* xa = x;
+    const float* wa = w_ih;
+    const int64_t ink = srk::pad4(in);
+    if (srk::padded_in(in)) {   // zero-pad the input width to a multiple of 4 (vector GEMM paths)
+      if (int rc = srk::pad_cols(x, BT, in, ws + L.xpad, s)) return rc;
+      if (int rc = srk::pad_cols(w_ih, 6 * H, in, ws + L.wpad, s)) return rc;
+      xa = ws + L.xpad;
+      wa = ws + L.wpad;
     }
+    if (!fuse) {
+      // gi[B*T, 6H] = x[B*T, in] * W_ih_cat[6H, in]^T + b_ih_cat (rev_cell: the forward direction's 3H columns)
+      GemmDesc g;
+      g.M = BT; g.N = rev_cell ? 3 * H : 6 * H; g.K = ink;
+      g.A = xa; g.lda = ink;
+      g.B = wa; g.ldb = ink; g.tb = true;
+      g.C = gi; g.ldc = 6 * H;
+      g.bias = b_ih; g.bias_mode = 1;
+      if (int rc = srk::gemm_f32(g, s)) return rc;
+    }
+    if (rev_cell) {
+      // gi[(b, T-1)][3H:6H] = x[b, T-1, :] * W_ih[1]^T + b_ih[1]: B strided rows, where the full GEMM puts them
+      GemmDesc g;
+      g.M = B; g.N = 3 * H; g.K = ink;
+      g.A = xa + (T - 1) * ink; g.lda = T * ink;
+      g.B = wa + 3 * H * ink; g.ldb = ink; g.tb = true;
+      g.C = gi + (T - 1) * 6 * H + 3 * H; g.ldc = T * 6 * H;
+      g.bias = b_ih + 3 * H; g.bias_mode = 1;
+      g.no_split = top_last == 3;   // mode 3: the full projection's sum order (wherever that GEMM runs unsplit)
+      if (int rc = srk::gemm_f32(g, s)) return rc;
+    }
+  }
+  if (path.persistent) {
+    srk::GruPArgs p = rec_args(B, T, H, w_hh, ws, L);
+    p.gi = gi; p.b_hh = b_hh; p.y = y; p.gates = gates; p.y16 = y16;
+    if (fuse) { p.x_in = x; p.w_ih = w_ih; p.b_ih = b_ih; p.in = (int)in; }
+    p.one_dir = rev_cell ? 1 : 0;
+    if (int rc = srk::gru_persistent_launch(p, path.fwd, false, s)) return rc;
+    if (rev_cell)   // after the recurrence: y_last's forward half is its last step
+      return srk::launch256(path.fwd.fast_cell ? srk::rev_cell_fwd_kernel<true> : srk::rev_cell_fwd_kernel<false>,
+                            B * H, s, gi, b_hh, B, T, H, y, y_last, gates);
     return SRK_OK;
   }
   srk::GruArgs a{};
@@ -752,12 +792,13 @@ int srk_gru_layer_fwd_x16(const float* x, const void* x16_in, int64_t B, int64_t
   SRK_API_BEGIN
   if (int rc = srk::check_dims(B, T, in, H)) return rc;
   SRK_REQUIRE(x && w_ih && w_hh && b_ih && b_hh && y && ws, SRK_ERR_INVALID, "gru_fwd: null pointer");
-  return layer_fwd(x, x16_in, B, T, in, H, w_ih, w_hh, b_ih, b_hh, y, ws, 0, nullptr, srk::as_stream(stream));
+  return layer_fwd(x, x16_in, B, T, in, H, w_ih, w_hh, b_ih, b_hh, y, ws, gru_path(B, T, in, H), 0, nullptr,
+                   srk::as_stream(stream));
   SRK_API_END
 }
 
 int64_t srk_gru_top_last_workspace_floats(int64_t B, int64_t T, int64_t in, int64_t H, int backward) {
-  return srk_gru_workspace_floats(B, T, in, H, backward) + (backward ? up64(B * T * 2 * H) : 0);
+  return gru_ws(B, T, in, H, backward != 0).top_total;
 }
 
 int srk_gru_top_last_fwd(const float* x, const void* x16_in, int64_t B, int64_t T, int64_t in, int64_t H,
@@ -768,14 +809,11 @@ int srk_gru_top_last_fwd(const float* x, const void* x16_in, int64_t B, int64_t 
   SRK_REQUIRE(x && w_ih && w_hh && b_ih && b_hh && y && y_last && ws && mode, SRK_ERR_INVALID,
               "gru_top_last_fwd: null pointer");
   hipStream_t s = srk::as_stream(stream);
-  *mode = top_last_mode(B, T, H);
-  if (int rc = layer_fwd(x, x16_in, B, T, in, H, w_ih, w_hh, b_ih, b_hh, y, ws, *mode, y_last, s)) return rc;
-  if (*mode < 2) {   // modes 0 and 1 ran the full layer: y_last is its row T-1
-    const int64_t n = B * 2 * H;
-    hipLaunchKernelGGL(srk::gather_last_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, y, B, (int)T,
-                       (int)(2 * H), y_last);
-    SRK_CHECK_HIP(hipGetLastError());
-  }
+  const GruPath path = gru_path(B, T, in, H);
+  *mode = path.top_last;
+  if (int rc = layer_fwd(x, x16_in, B, T, in, H, w_ih, w_hh, b_ih, b_hh, y, ws, path, *mode, y_last, s)) return rc;
+  if (*mode < 2)   // modes 0 and 1 ran the full layer: y_last is its row T-1
+    return srk::launch256(srk::gather_last_kernel, B * 2 * H, s, y, B, T, 2 * H, y_last);
   return SRK_OK;
   SRK_API_END
 }
@@ -796,196 +834,137 @@ int srk_gru_layer_bwd(const float* x, int64_t B, int64_t T, int64_t in, int64_t 
 // zero-fills those dgi rows and keeps the full dW_ih / dx GEMMs: every result then has the full layer's bits.
 static int layer_bwd(const float* x, const void* x16_in, int64_t B, int64_t T, int64_t in, int64_t H,
                      const float* w_ih, const float* w_hh, const float* y, const float* ws_fwd, const float* dy,
-                     const float* dy_last, int top_last, float* dx, float* dw_ih, float* dw_hh, float* db_ih,
-                     float* db_hh, int accumulate, float* ws, hipStream_t s) {
+                     const float* dy_last, const GruPath& path, int top_last, float* dx, float* dw_ih, float* dw_hh,
+                     float* db_ih, float* db_hh, int accumulate, float* ws, hipStream_t s) {
+  SRK_REQUIRE(!top_last || (path.persistent && !path.h16 && dy_last), SRK_ERR_INTERNAL,
+              "gru_bwd: top_last off the fp32 persistent path");
   const int64_t BT = B * T;
-  if (use_h16(B, T, in, H)) {
-    // 16-bit path: the kernel writes dgi16 / dgh16 (aliasing the fp32 dgi region) and the bias-
-    // gradient partials; every GEMM reads 16-bit operands (x16 / W16 / y16 from the forward).
-    const int64_t in8 = in8_of(in);
-    const uint16_t* x16 = reinterpret_cast<const uint16_t*>(ws_fwd + pad_end(B, T, in, H, 0));
-    const uint16_t* w16 = x16 + 2 * up64(BT * in8 / 2 + 1);
-    const uint16_t* y16 = w16 + 2 * up64(6 * H * in8 / 2 + 1);
-    if (x16_in) x16 = static_cast<const uint16_t*>(x16_in);   // the forward's ready copy (srk_gru_layer_fwd_x16)
-    uint16_t* dgi16 = reinterpret_cast<uint16_t*>(ws);
-    uint16_t* dgh16 = dgi16 + BT * 6 * H;
-    float* part = ws + pad_end(B, T, in, H, 1);
-    const int64_t chunks = (B + 255) / 256;
-    float* dwpad = part + up64(chunks * 8 * 2 * 4 * H);
-    float* dxpad = dwpad + up64(6 * H * in8);
-    srk::GruPArgs p{};
-    p.B = (int)B; p.T = (int)T; p.H = (int)H;
-    p.w_hh = w_hh; p.y_in = y; p.gates = const_cast<float*>(ws_fwd + BT * 6 * H); p.dy = dy;
-    p.dgi16 = dgi16; p.dgh16 = dgh16; p.dbias = part;
-    p.xbuf = ws + bwd_xbuf_off(B, T, H);
-    p.counters = reinterpret_cast<unsigned*>(ws + bwd_counter_off(B, T, H));
-    int rc;
-    // the recurrent weight gradient accumulated inside the recurrence kernel (partials per row group)
-    const int dw_parts = srk::gru_dwhh_fused_parts(B, T);
-    if (dw_parts) {
-      if ((rc = srk::gru_scratch((size_t)dw_parts * 2 * 3 * H * H, &p.dw_part))) return rc;
-      p.y16_in = y16;
-    }
-    if ((rc = srk::gru_persistent_launch(p, true, s))) return rc;
-    const int prows = srk::gru_bias_part_rows(B);
-    if (dw_parts) {   // dW_hh and the bias gradients from their partials: one launch
-      const int64_t per_dir = 3 * H * H, n4 = 2 * per_dir / 4;
-      const int dw_blocks = (int)((n4 + 255) / 256);
-      srk::ProfScope prof("gru_dwhh_reduce", s, 4.0 * (dw_parts + 2) * 2 * per_dir);
-      hipLaunchKernelGGL(srk::dwhh_dbias_reduce_kernel, dim3((unsigned)(dw_blocks + (6 * H + 255) / 256)), dim3(256),
-                         0, s, p.dw_part, dw_parts, (int)B, per_dir, dw_hh, (int)accumulate, dw_blocks, part,
-                         (int)(chunks * (256 / prows)), (int)H, prows, db_ih, db_hh);
+  const GruWs L = gru_ws(B, T, in, H, true), F = gru_ws(B, T, in, H, false);   // F: the forward's, inside ws_fwd
+  const bool h16 = path.h16;
+  float* dgi = ws + L.dgi;
+  float* dgh = ws + L.dgh;
+  float* dgh_edge = ws + L.dgh_edge;
+  float* gates = const_cast<float*>(ws_fwd + F.gates);
+  // The operand set of the layer's GEMMs: fp32 at width in4, or (16-bit path) 16-bit at width in8 — dgi16 / dgh16
+  // from the kernel, x16 / W16 / y16 from the forward (x16_in: its ready copy, srk_gru_layer_fwd_x16).  pad: dW_ih
+  // and dx come out at that width in a pad buffer and their first `in` columns go to the caller's tensors.
+  struct Mat {
+    const float* f;
+    const uint16_t* h;
+    Mat at(int64_t off) const { return {f ? f + off : nullptr, h ? h + off : nullptr}; }
+  };
+  const auto set_a = [](GemmDesc& g, Mat m) { g.A = m.f; g.A16 = m.h; };
+  const auto set_b = [](GemmDesc& g, Mat m) { g.B = m.f; g.B16 = m.h; };
+  const int64_t ld = h16 ? in8_of(in) : srk::pad4(in);
+  const bool pad = ld != in;
+  float* wpad = pad && !h16 ? ws + L.wpad : nullptr;                // fp32: [6H][in4]
+  float* dwpad = pad ? ws + (h16 ? L.dwpad8 : L.dwpad) : nullptr;   // [6H][ld]
+  float* dxpad = pad ? ws + (h16 ? L.dxpad8 : L.dxpad) : nullptr;   // [BT][ld]
+  Mat m_dgi{dgi, nullptr}, m_dgh{dgh, nullptr}, m_x{pad ? ws_fwd + F.xpad : x, nullptr},
+      m_w{pad ? wpad : w_ih, nullptr}, m_y{y, nullptr};
+  if (h16) {
+    m_dgi = {nullptr, u16(ws + L.dgi)};
+    m_dgh = {nullptr, u16(ws + L.dgh16)};
+    m_x = {nullptr, x16_in ? static_cast<const uint16_t*>(x16_in) : u16(ws_fwd + F.x16)};
+    m_w = {nullptr, u16(ws_fwd + F.w16)};   // (rounded below where the fused-projection forward left it unwritten)
+    m_y = {nullptr, u16(ws_fwd + F.y16)};
+  }
+  int rc;
+  // the recurrent weight gradient accumulated inside the recurrence kernel (partials per row group)
+  const int dw_parts = h16 ? path.bwd.dw_parts : 0;
+  if (path.persistent) {
+    srk::GruPArgs p = rec_args(B, T, H, w_hh, ws, L);
+    p.y_in = y; p.gates = gates; p.dy = dy;
+    if (h16) {   // the kernel writes dgi16 / dgh16 and the bias-gradient partials
+      p.dgi16 = const_cast<uint16_t*>(m_dgi.h); p.dgh16 = const_cast<uint16_t*>(m_dgh.h); p.dbias = ws + L.part;
+      if (dw_parts) {
+        if ((rc = srk::gru_scratch((size_t)dw_parts * 2 * 3 * H * H, &p.dw_part))) return rc;
+        p.y16_in = m_y.h;
+      }
     } else {
-      hipLaunchKernelGGL(srk::dbias_reduce_kernel, dim3((unsigned)((6 * H + 255) / 256)), dim3(256), 0, s, part,
-                         (int)(chunks * (256 / prows)), (int)B, (int)H, prows, db_ih, db_hh, accumulate);
+      p.dgi = dgi; p.dgh = dgh; p.dgh_edge = dgh_edge;
+      p.one_dir = top_last >= 2 ? 1 : 0;
+    }
+    if ((rc = srk::gru_persistent_launch(p, path.bwd, true, s))) return rc;
+    if (h16) {
+      const int prows = path.bwd.bias_part_rows, bparts = (int)((B + 255) / 256 * (256 / prows));
+      if (dw_parts) {   // dW_hh and the bias gradients from their partials: one launch
+        const int64_t per_dir = 3 * H * H, n4 = 2 * per_dir / 4;
+        const int dw_blocks = (int)((n4 + 255) / 256);
+        srk::ProfScope prof("gru_dwhh_reduce", s, 4.0 * (dw_parts + 2) * 2 * per_dir);
+        hipLaunchKernelGGL(srk::dwhh_dbias_reduce_kernel, dim3((unsigned)(dw_blocks + (6 * H + 255) / 256)), dim3(256),
+                           0, s, p.dw_part, dw_parts, (int)B, per_dir, dw_hh, (int)accumulate, dw_blocks, p.dbias,
+                           bparts, (int)H, prows, db_ih, db_hh);
+        SRK_CHECK_HIP(hipGetLastError());
+      } else if ((rc = srk::launch256(srk::dbias_reduce_kernel, 6 * H, s, p.dbias, bparts, B, H, prows, db_ih, db_hh,
+                                      accumulate))) {
+        return rc;
+      }
+    }
+    // top_last == 3: the full dW_ih / dx GEMMs below read whole dgi rows: the reverse columns' true value, zero
+    if (top_last == 3 && (rc = srk::launch256(srk::zero_cols_kernel, BT * 3 * H / 4, s, dgi, BT, 3 * H, 3 * H, 6 * H)))
+      return rc;
+    if (top_last >= 2 && (rc = srk::launch256(srk::rev_cell_bwd_kernel, B * H, s, gates, dy_last, B, T, H, dgi, dgh_edge)))
+      return rc;
+  } else {
+    srk::GruArgs a{};
+    a.B = (int)B; a.T = (int)T; a.H = (int)H; a.in = (int)in;
+    a.y_in = y; a.w_hh = w_hh; a.gates = gates;
+    a.dy = dy; a.dgi = dgi; a.dgh = dgh; a.dgh_edge = dgh_edge; a.dhz = ws + L.dhz;
+    a.G = (int)((B + srk::kRows - 1) / srk::kRows);
+    a.S = (int)(H / srk::kUnits);
+    const dim3 grid((unsigned)(2 * a.G * a.S));
+    for (int step = 0; step < T; ++step) {
+      srk::ProfScope prof("gru_bwd_step", s, step > 0 ? 2.0 * 2.0 * (double)B * 3 * H * H : 0.0);   // 2 dirs x [B,3H]x[3H,H]
+      hipLaunchKernelGGL(srk::gru_bwd_step_kernel, grid, dim3(256), 0, s, a, step);
     }
     SRK_CHECK_HIP(hipGetLastError());
-    const float beta = accumulate ? 1.f : 0.f;
-    {  // dW_ih [6H, in] = dgi16^T x16
-      GemmDesc g;
-      g.M = 6 * H; g.N = in8; g.K = BT;
-      g.A16 = dgi16; g.lda = 6 * H; g.ta = true;
-      g.B16 = x16; g.ldb = in8;
-      g.C = in8 == in ? dw_ih : dwpad; g.ldc = in8; g.beta = in8 == in ? beta : 0.f;
-      if ((rc = srk::gemm_f32(g, s))) return rc;
-      if (in8 != in) {
-        const int64_t n = 6 * H * in;
-        hipLaunchKernelGGL(srk::unpad_cols_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dwpad, 6 * H,
-                           (int)in8, dw_ih, (int)in, (int)accumulate);
-        SRK_CHECK_HIP(hipGetLastError());
-      }
-    }
-    {   // dW_hh[dir] = dgh16[dir]^T h_prev16 (edge rows of dgh16 are zero), both directions in ONE
-        // batched launch: dir 0 pairs dgh16 row r + 1 with y16 row r, dir 1 dgh16 row r with y16 row
-        // r + 1 (its reverse half); a 24-tile grid split 10 ways fills the CUs where two 12-tile
-        // launches ran one after the other
-      GemmDesc g;
-      g.M = 3 * H; g.N = H; g.K = BT - 1;
-      g.ta = true; g.lda = 3 * H; g.ldb = 2 * H;
-      g.A16 = dgh16 + 3 * H;                 // dir 1: dgh16 + BT 3H
-      g.B16 = y16;                           // dir 1: y16 + 3H (row 1, reverse half)
-      g.C = dw_hh; g.ldc = H; g.beta = beta;
-      g.batch = 2; g.sA = BT * 3 * H - 3 * H; g.sB = 3 * H; g.sC = 3 * H * H;
-      if (dw_parts) {
-        // done: the recurrence kernel accumulated it (dwhh_dbias_reduce_kernel above)
-      } else if (g.K > 0 && srk::g_opt_gru_dwhh_batched) {
-        if ((rc = srk::gemm_f32(g, s))) return rc;
-      } else if (g.K > 0) {   // one launch per direction (A/B and tests)
-        g.batch = 1;
-        for (int dir = 0; dir < 2; ++dir, g.A16 += g.sA, g.B16 += g.sB, g.C += g.sC)
-          if ((rc = srk::gemm_f32(g, s))) return rc;
-      } else if (!accumulate) {
-        SRK_CHECK_HIP(hipMemsetAsync(g.C, 0, sizeof(float) * 2 * 3 * H * H, s));
-      }
-    }
-    if (dx) {   // dx [BT, in] = dgi16 W16
-      if (in <= srk::kFusedIn) {   // the fused-projection forward left W16 unwritten: round it here
-        if ((rc = srk::to16(w_ih, 6 * H, in, const_cast<uint16_t*>(w16), in8, s))) return rc;
-      }
-      GemmDesc g;
-      g.M = BT; g.N = in8; g.K = 6 * H;
-      g.A16 = dgi16; g.lda = 6 * H;
-      g.B16 = w16; g.ldb = in8;
-      g.C = in8 == in ? dx : dxpad; g.ldc = in8;
-      if ((rc = srk::gemm_f32(g, s))) return rc;
-      if (in8 != in) {
-        const int64_t n = BT * in;
-        hipLaunchKernelGGL(srk::unpad_cols_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dxpad, BT,
-                           (int)in8, dx, (int)in, 0);
-        SRK_CHECK_HIP(hipGetLastError());
-      }
-    }
-    return SRK_OK;
-  }
-  float* dgi = ws;
-  float* dgh = dgi + BT * 6 * H;
-  float* dgh_edge = dgh + 2 * BT * 3 * H;
-  float* dhz = dgh_edge + 2 * B * 3 * H;
-  srk::GruArgs a{};
-  a.B = (int)B; a.T = (int)T; a.H = (int)H; a.in = (int)in;
-  a.y_in = y; a.w_hh = w_hh; a.gates = const_cast<float*>(ws_fwd + BT * 6 * H);
-  a.dy = dy; a.dgi = dgi; a.dgh = dgh; a.dgh_edge = dgh_edge; a.dhz = dhz;
-  a.G = (int)((B + srk::kRows - 1) / srk::kRows);
-  a.S = (int)(H / srk::kUnits);
-  const bool persistent = persistent_pair(B, T, H);   // as the forward decided (the gates' layout)
-  SRK_REQUIRE(!top_last || (persistent && dy_last), SRK_ERR_INTERNAL, "gru_bwd: top_last off the persistent path");
-  if (persistent) {
-    srk::GruPArgs p{};
-    p.B = (int)B; p.T = (int)T; p.H = (int)H;
-    p.w_hh = w_hh; p.y_in = y; p.gates = a.gates; p.dy = dy; p.dgi = dgi; p.dgh = dgh; p.dgh_edge = dgh_edge;
-    p.xbuf = ws + bwd_xbuf_off(B, T, H);
-    p.counters = reinterpret_cast<unsigned*>(ws + bwd_counter_off(B, T, H));
-    p.one_dir = top_last >= 2 ? 1 : 0;
-    if (int rc = srk::gru_persistent_launch(p, true, s)) return rc;
-    if (top_last == 3) {   // the full dW_ih / dx GEMMs below read whole dgi rows: the reverse columns' true value, zero
-      const int64_t n4 = BT * 3 * H / 4;
-      hipLaunchKernelGGL(srk::zero_cols_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, dgi, BT,
-                         (int)(3 * H), (int)(3 * H), (int)(6 * H));
-      SRK_CHECK_HIP(hipGetLastError());
-    }
-    if (top_last >= 2) {
-      hipLaunchKernelGGL(srk::rev_cell_bwd_kernel, dim3((unsigned)((B * H + 255) / 256)), dim3(256), 0, s, a.gates,
-                         dy_last, B, (int)T, (int)H, dgi, dgh_edge);
-      SRK_CHECK_HIP(hipGetLastError());
-    }
-  } else {
-  const dim3 grid((unsigned)(2 * a.G * a.S));
-  for (int step = 0; step < T; ++step) {
-    srk::ProfScope prof("gru_bwd_step", s, step > 0 ? 2.0 * 2.0 * (double)B * 3 * H * H : 0.0);   // 2 dirs x [B,3H]x[3H,H]
-    hipLaunchKernelGGL(srk::gru_bwd_step_kernel, grid, dim3(256), 0, s, a, step);
-  }
-  SRK_CHECK_HIP(hipGetLastError());
   }
 
-  int rc;
   const float beta = accumulate ? 1.f : 0.f;   // autograd .grad accumulation in the GEMM epilogues
-  const bool pad = srk::padded_in(in);
-  const int64_t in4 = srk::pad4(in);
-  float* wpad = pad ? ws + pad_off(B, T, H, 1) : nullptr;   // [6H][in4]
-  float* dwpad = pad ? wpad + 6 * H * in4 : nullptr;         // [6H][in4]
-  float* dxpad = pad ? dwpad + 6 * H * in4 : nullptr;        // [BT][in4]
+  // fp32: the bias gradients are fused row sums of the GEMMs' A operands (16-bit: from the kernel's partials, above)
+  const bool sums = !h16;
   // modes 1 and 2: the reverse direction's dgi taken as its B live rows (b, T-1), lda = T 6H; mode 3 keeps the full
   // dW_ih / dx GEMMs (their sums' order, so their bits) and drops only the reverse dW_hh
   const bool rev_last = top_last == 1 || top_last == 2;
-  const float* dgi_rev = dgi + (T - 1) * 6 * H + 3 * H;
-  {  // dW_ih_cat[6H, in] = dgi^T [6H, BT] * x [BT, in]; db_ih fused as the row sums of dgi^T
+  const Mat m_dgi_rev = m_dgi.at((T - 1) * 6 * H + 3 * H);
+  {  // dW_ih_cat[6H, in] = dgi^T [6H, BT] * x [BT, in] (the forward's padded x); fp32: db_ih = the row sums of dgi^T
     GemmDesc g;
-    g.M = rev_last ? 3 * H : 6 * H; g.N = pad ? in4 : in; g.K = BT;
-    g.A = dgi; g.lda = 6 * H; g.ta = true;
-    g.B = pad ? ws_fwd + pad_off(B, T, H, 0) : x; g.ldb = pad ? in4 : in;   // the forward's padded x
-    g.C = pad ? dwpad : dw_ih; g.ldc = pad ? in4 : in; g.beta = pad ? 0.f : beta;
-    g.rowsum = db_ih; g.rowsum_beta = beta;
+    g.M = rev_last ? 3 * H : 6 * H; g.N = ld; g.K = BT;
+    set_a(g, m_dgi); g.lda = 6 * H; g.ta = true;
+    set_b(g, m_x); g.ldb = ld;
+    g.C = pad ? dwpad : dw_ih; g.ldc = ld; g.beta = pad ? 0.f : beta;
+    if (sums) { g.rowsum = db_ih; g.rowsum_beta = beta; }
     if ((rc = srk::gemm_f32(g, s))) return rc;
     if (rev_last) {   // the reverse half from its B live rows against x[:, T-1, :]
       g.K = B;
-      g.A = dgi_rev; g.lda = T * 6 * H;
-      g.B += (T - 1) * g.ldb; g.ldb *= T;
+      set_a(g, m_dgi_rev); g.lda = T * 6 * H;
+      set_b(g, m_x.at((T - 1) * ld)); g.ldb = T * ld;
       g.C += 3 * H * g.ldc;
       g.rowsum = db_ih + 3 * H;
       if ((rc = srk::gemm_f32(g, s))) return rc;
     }
-    if (pad) {
-      const int64_t n = 6 * H * in;
-      hipLaunchKernelGGL(srk::unpad_cols_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dwpad, 6 * H,
-                         (int)in4, dw_ih, (int)in, (int)accumulate);
-      SRK_CHECK_HIP(hipGetLastError());
-    }
+    if (pad && (rc = srk::launch256(srk::unpad_cols_kernel, 6 * H * in, s, dwpad, 6 * H, ld, dw_ih, in, accumulate)))
+      return rc;
   }
-  {
+  if (!dw_parts) {   // (else the recurrence kernel accumulated it: dwhh_dbias_reduce_kernel above)
     // dW_hh[dir][3H, H] = sum_(b,t) dgh[b][t]^T h_prev[b][t]; h_prev of row (b,t) is y row (b,t-1)
     // (dir 0) or (b,t+1) (dir 1); the edge rows of dgh are zero so the batch seams contribute 0.
-    // db_hh = row sums of dgh^T (fused) + the edge rows kept aside in dgh_edge.  Both directions run
-    // as ONE batch-2 launch (dir 1 = dir 0's operands + sA / sB; option gru_dwhh_batched).
+    // fp32: db_hh = row sums of dgh^T (fused) + the edge rows kept aside in dgh_edge.  Both directions run
+    // as ONE batch-2 launch (dir 1 = dir 0's operands + sA / sB; option gru_dwhh_batched): a 24-tile grid
+    // split 10 ways fills the CUs where two 12-tile launches ran one after the other.
     GemmDesc g;
     g.M = 3 * H; g.N = H; g.K = BT - 1;
     g.ta = true; g.lda = 3 * H; g.ldb = 2 * H;
-    g.A = dgh + 3 * H;      // dir 1: dgh + BT 3H
-    g.B = y;                // dir 1: y + 3H (row 1, reverse half)
+    const Mat a0 = m_dgh.at(3 * H);   // dir 1: dgh + BT 3H
+    const Mat b0 = m_y;               // dir 1: y + 3H (row 1, reverse half)
+    set_a(g, a0);
+    set_b(g, b0);
     g.C = dw_hh; g.ldc = H; g.beta = beta;
-    g.rowsum = db_hh; g.rowsum_beta = beta;
-    g.batch = 2; g.sA = BT * 3 * H - 3 * H; g.sB = 3 * H; g.sC = 3 * H * H; g.sRS = 3 * H;
+    g.batch = 2; g.sA = BT * 3 * H - 3 * H; g.sB = 3 * H; g.sC = 3 * H * H;
+    if (sums) { g.rowsum = db_hh; g.rowsum_beta = beta; g.sRS = 3 * H; }
     // (the batched row sums exist on the ping-pong kernel only: 16-B rows, 32-bit buffer offsets)
-    const bool batched = srk::g_opt_gru_dwhh_batched && srk::gemm_f32_batched_rowsum_ok(g);
+    const bool batched = srk::g_opt_gru_dwhh_batched && (!sums || srk::gemm_f32_batched_rowsum_ok(g));
     if (top_last) {   // the forward direction alone; dW_hh[1] = 0 and db_hh[1] = the column sums of dgh_edge[1] below
       g.batch = 1;
       // mode 3: the kernel and K split of the two-direction launch, so its bits for dW_hh[0]
@@ -1002,40 +981,45 @@ static int layer_bwd(const float* x, const void* x16_in, int64_t B, int64_t T, i
       }
     } else if (g.K > 0 && batched) {
       if ((rc = srk::gemm_f32(g, s))) return rc;
-    } else if (g.K > 0) {
+    } else if (g.K > 0) {   // one launch per direction (A/B and tests)
       g.batch = 1;
-      for (int dir = 0; dir < 2; ++dir, g.A += g.sA, g.B += g.sB, g.C += g.sC, g.rowsum += g.sRS)
+      for (int dir = 0; dir < 2; ++dir) {
+        set_a(g, a0.at(dir * g.sA));
+        set_b(g, b0.at(dir * g.sB));
+        g.C = dw_hh + dir * g.sC;
+        if (sums) g.rowsum = db_hh + dir * g.sRS;
         if ((rc = srk::gemm_f32(g, s))) return rc;
+      }
     } else if (!accumulate) {
       SRK_CHECK_HIP(hipMemsetAsync(dw_hh, 0, sizeof(float) * 2 * 3 * H * H, s));
-      SRK_CHECK_HIP(hipMemsetAsync(db_hh, 0, sizeof(float) * 2 * 3 * H, s));
+      if (sums) SRK_CHECK_HIP(hipMemsetAsync(db_hh, 0, sizeof(float) * 2 * 3 * H, s));
     }
+  }
+  if (sums)
     for (int dir = 0; dir < 2; ++dir)
       if ((rc = srk::colsum_f32(dgh_edge + (size_t)dir * B * 3 * H, B, 3 * H, 3 * H, db_hh + dir * 3 * H, 1.f, s)))
         return rc;
-  }
   if (dx) {  // dx[BT, in] = dgi[BT, 6H] * W_ih_cat[6H, in]
+    if (h16 && in <= srk::kFusedIn) {   // the fused-projection forward left W16 unwritten: round it here
+      if ((rc = srk::to16(w_ih, 6 * H, in, const_cast<uint16_t*>(m_w.h), ld, s))) return rc;
+    } else if (!h16 && pad) {
+      if ((rc = srk::pad_cols(w_ih, 6 * H, in, wpad, s))) return rc;
+    }
     GemmDesc g;
-    g.M = BT; g.N = pad ? in4 : in; g.K = rev_last ? 3 * H : 6 * H;
-    g.A = dgi; g.lda = 6 * H;
-    if (pad && (rc = srk::pad_cols(w_ih, 6 * H, in, wpad, s))) return rc;
-    g.B = pad ? wpad : w_ih; g.ldb = pad ? in4 : in;
-    g.C = pad ? dxpad : dx; g.ldc = pad ? in4 : in;
+    g.M = BT; g.N = ld; g.K = rev_last ? 3 * H : 6 * H;
+    set_a(g, m_dgi); g.lda = 6 * H;
+    set_b(g, m_w); g.ldb = ld;
+    g.C = pad ? dxpad : dx; g.ldc = ld;
     if ((rc = srk::gemm_f32(g, s))) return rc;
     if (rev_last) {   // rows (b, T-1) += dgi_rev_last * W_ih[1]
       g.M = B;
-      g.A = dgi_rev; g.lda = T * 6 * H;
-      g.B += 3 * H * g.ldb;
+      set_a(g, m_dgi_rev); g.lda = T * 6 * H;
+      set_b(g, m_w.at(3 * H * ld));
       g.C += (T - 1) * g.ldc; g.ldc *= T;
       g.beta = 1.f;
       if ((rc = srk::gemm_f32(g, s))) return rc;
     }
-    if (pad) {
-      const int64_t n = BT * in;
-      hipLaunchKernelGGL(srk::unpad_cols_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dxpad, BT,
-                         (int)in4, dx, (int)in, 0);
-      SRK_CHECK_HIP(hipGetLastError());
-    }
+    if (pad && (rc = srk::launch256(srk::unpad_cols_kernel, BT * in, s, dxpad, BT, ld, dx, in, 0))) return rc;
   }
   return SRK_OK;
 }
@@ -1048,8 +1032,8 @@ int srk_gru_layer_bwd_x16(const float* x, const void* x16_in, int64_t B, int64_t
   if (int rc = srk::check_dims(B, T, in, H)) return rc;
   SRK_REQUIRE(x && w_ih && w_hh && y && ws_fwd && dy && dw_ih && dw_hh && db_ih && db_hh && ws, SRK_ERR_INVALID,
               "gru_bwd: null pointer");
-  return layer_bwd(x, x16_in, B, T, in, H, w_ih, w_hh, y, ws_fwd, dy, nullptr, 0, dx, dw_ih, dw_hh, db_ih, db_hh,
-                   accumulate, ws, srk::as_stream(stream));
+  return layer_bwd(x, x16_in, B, T, in, H, w_ih, w_hh, y, ws_fwd, dy, nullptr, gru_path(B, T, in, H), 0, dx, dw_ih,
+                   dw_hh, db_ih, db_hh, accumulate, ws, srk::as_stream(stream));
   SRK_API_END
 }
 
@@ -1063,19 +1047,17 @@ int srk_gru_top_last_bwd(const float* x, const void* x16_in, int64_t B, int64_t 
               "gru_top_last_bwd: null pointer");
   SRK_REQUIRE(mode >= 0 && mode <= 3, SRK_ERR_INVALID, "gru_top_last_bwd: mode must be the forward's (0 .. 3)");
   // modes 1 .. 3 exist on the fp32 persistent path only; the forward chose the mode there
-  SRK_REQUIRE(mode == 0 || top_last_path(B, T, H), SRK_ERR_INVALID,
+  const GruPath path = gru_path(B, T, in, H);
+  SRK_REQUIRE(mode == 0 || path.top_last_ok, SRK_ERR_INVALID,
               "gru_top_last_bwd: mode %d needs the fp32 persistent path its forward ran on", mode);
   hipStream_t s = srk::as_stream(stream);
   // the [B][T][2H] gradient the recurrence reads: zeros and the last row (what last_step's backward builds)
-  float* dy = ws + srk_gru_workspace_floats(B, T, in, H, 1);
-  const int64_t n4 = B * T * 2 * H / 4;
-  hipLaunchKernelGGL(srk::pad_last_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, dy_last, B, (int)T,
-                     (int)(2 * H), dy);
-  SRK_CHECK_HIP(hipGetLastError());
+  float* dy = ws + gru_ws(B, T, in, H, true).dy;
+  if (int rc = srk::launch256(srk::pad_last_kernel, B * T * 2 * H / 4, s, dy_last, B, T, 2 * H, dy)) return rc;
   // mode 0 (16-bit precisions, H != 512, no persistent kernels): the full layer backward on that dy, exactly
   // what last_step(srk_gru_layer_fwd) backpropagates
-  return layer_bwd(x, x16_in, B, T, in, H, w_ih, w_hh, y, ws_fwd, dy, dy_last, mode, dx, dw_ih, dw_hh, db_ih, db_hh,
-                   accumulate, ws, s);
+  return layer_bwd(x, x16_in, B, T, in, H, w_ih, w_hh, y, ws_fwd, dy, dy_last, path, mode, dx, dw_ih, dw_hh, db_ih,
+                   db_hh, accumulate, ws, s);
   SRK_API_END
 }
 

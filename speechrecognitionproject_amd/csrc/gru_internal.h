@@ -82,13 +82,53 @@ __device__ __forceinline__ float tanh_fast(float x) { return 2.0f * sigmoid_fast
 
 size_t fwd_lds_bytes(int H);
 size_t bwd_lds_bytes(int H);
-// 1 if the persistent kernels can run this layer (H, co-residency, 32-bit buffer offsets).
-int gru_persistent_supported(int64_t B, int64_t T, int64_t H, bool backward);
-// Enqueue the whole recurrence (all T steps; batch split into co-resident chunks).
-int gru_persistent_launch(GruPArgs a, bool backward, hipStream_t s);
-// 1 if the fp32 persistent forward evaluates its cells with sigmoid_fast / tanh_fast (the two-chain kernel with
-// option gru_fp32_fast_cell), 0 if with the libm forms.
-int gru_fp32_fast_cell();
+
+// Which kernel runs the recurrence of one direction of travel (forward or backward pass) of a layer.
+enum GruVariant {
+  kGruStep = 0,   // no persistent kernel: the per-step kernels of gru.hip
+  kGruF32,        // fp32, 4 waves
+  kGruDc,         // fp32, two row chains per workgroup (option gru_fp32_dual_chain), gi / dgi in memory
+  kGruDcFused,    // the two-chain forward with the fused input projection (in <= kFusedIn)
+  kGruLp,         // 16-bit, 64 rows x 16 units
+  kGruLp2,        // 16-bit, 32 x 32 (option gru_lp_32x32)
+  kGruLp2Wide,    // its 64-row form (RB = 4) for B > 256: up to 512 rows per launch (option gru_lp_wide)
+  kGruLp2Dw,      // the 32 x 32 backward with the recurrent weight gradient fused in (option gru_dwhh_fused)
+  kGruLp2Ow,      // the 32 x 32 forward with output / input worker waves (option gru_fwd_worker)
+};
+// The option values the selection rule reads (gru_opts(): the current srk_set_option state)
+struct GruOpts {
+  int persistent, lp2, lp_wide, dc, fast_cell, dwhh_fused, fwd_worker;
+};
+GruOpts gru_opts();
+// "Does variant v's kernel (at prec, this direction of travel) fit one workgroup per CU?": > 0 yes.  For the base
+// kernels (kGruF32, kGruLp) `grid` workgroups must also be co-resident on the device; kGruDc asks for all three
+// two-chain kernels.  gru_fit_measured is the device's answer (cached per kernel, one query per process); the
+// host-side audit passes "everything fits".
+using GruFitFn = int (*)(GruVariant v, int prec, bool backward, int grid);
+int gru_fit_measured(GruVariant v, int prec, bool backward, int grid);
+// The launch plan of one recurrence: everything gru_persistent_launch, the workspace users in gru.hip and
+// srk_gru_audit_words need to know about the variant.
+struct GruRecPlan {
+  GruVariant variant = kGruStep;
+  int prec = 0;
+  const void* kernel = nullptr;   // void (*)(GruPArgs)
+  int block = 0;
+  size_t lds = 0;
+  int rows_per_launch = 0;   // batch rows per launch (chunk)
+  int rows_g = 0;            // batch rows per workgroup group
+  int slices = 0;            // unit slices (workgroups per group and direction)
+  int bias_part_rows = 0;    // 16-bit backward: batch rows per bias-gradient partial (256-row chunks)
+  int dw_parts = 0;          // kGruLp2Dw: partials of dW_hh the kernel writes (chunks x 8), else 0
+  bool fast_cell = false;    // fp32 forward cells evaluated with sigmoid_fast / tanh_fast (two-chain kernel + option)
+  const char* suffix = "";   // of the profiler detail string
+};
+// THE selection rule.  in_fused: the input width when the forward kernel projects the input itself, else 0;
+// out16: the launch has its 16-bit outputs (forward y16, backward dgi16 / dgh16).  variant == kGruStep when the
+// persistent kernels cannot run this layer (option off, H, 32-bit buffer offsets, co-residency).
+GruRecPlan gru_rec_plan(int64_t B, int64_t T, int64_t H, int in_fused, int prec, bool backward, bool out16,
+                        const GruOpts& o, GruFitFn fits);
+// Enqueue the whole recurrence (all T steps; batch split into the plan's co-resident chunks).
+int gru_persistent_launch(GruPArgs a, const GruRecPlan& plan, bool backward, hipStream_t s);
 
 // Runtime options (srk_set_option): persistent GRU recurrence on/off (default on).
 extern int g_opt_gru_persistent;
@@ -101,13 +141,7 @@ extern int g_opt_gru_dc;                       // fp32 recurrence: two independe
 extern unsigned g_opt_gru_dc_offset;            // chain-1 start delay (ticks of 10 ns), default 200 (2 us)
 extern int g_opt_gru_fast_cell;                 // fp32 two-chain forward: hardware exp / rcp cell math (default 1)
 extern int g_opt_gru_dc_prio;                   // fp32 two-chain kernels: static priority of one chain (0, 1, 2)
-// Batch rows per bias-gradient partial of the 16-bit backward kernel (32 or 64; 256-row launch chunks).
-int gru_bias_part_rows(int64_t B);
-// Partials of dW_hh the 16-bit backward kernel would write with the fused recurrent weight gradient
-// (option gru_dwhh_fused; 32 x 32 workgroups, 256-row chunks): chunks x 8, or 0 when it does not apply
-// (fp32, the 64-row workgroups of B > 256, the kernel not fitting one workgroup per CU, T < 2).
-int gru_dwhh_fused_parts(int64_t B, int64_t T);
-extern int g_opt_gru_dwhh_fused;               // fused recurrent weight gradient in the 16-bit backward (default 1)
+extern int g_opt_gru_dwhh_fused;             // fused recurrent weight gradient in the 16-bit backward (default 1)
 extern int g_opt_gru_fwd_worker;               // 16-bit forward: output / input worker waves (default 0 until measured)
 // Last-step top layer (srk_gru_top_last_*, fp32 persistent path): 0 = the full layer, 1 = the backward GEMMs
 // without their all-zero reverse-direction parts, 2 = also the reverse direction as its one live cell, 3 = that cell

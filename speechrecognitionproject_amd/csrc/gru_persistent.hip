@@ -31,6 +31,7 @@
 // training.py's loss flush and bench.py check it and raise.
 #include <cstdlib>
 #include <type_traits>
+#include <map>
 #include <mutex>
 #include <utility>
 
@@ -2219,135 +2220,96 @@ size_t lp2_lds_bytes(int H, bool backward, int RB, bool dw = false, bool ow = fa
   return std::max<size_t>(need, 96 * 1024);   // one workgroup per CU (see lds_bytes)
 }
 
+// The one table (variant, direction of travel, precision) -> kernel and the shape it is launched with.
+struct RecKernel {
+  const void* fn;   // void (*)(GruPArgs)
+  int block;
+  size_t lds;
+  const char* suffix;
+};
+template <class K>
+const void* kp(K* k) { return reinterpret_cast<const void*>(k); }
+
 template <int H>
-const void* lp2_kernel_ptr(bool backward, int prec, int RB) {
-  if (RB == 4) {
-    if (prec == kPrecF16)
-      return backward ? reinterpret_cast<const void*>(gru_bwd_persistent_lp2_kernel<H, true, 4>)
-                      : reinterpret_cast<const void*>(gru_fwd_persistent_lp2_kernel<H, true, 4>);
-    return backward ? reinterpret_cast<const void*>(gru_bwd_persistent_lp2_kernel<H, false, 4>)
-                    : reinterpret_cast<const void*>(gru_fwd_persistent_lp2_kernel<H, false, 4>);
+RecKernel rec_kernel(GruVariant v, bool bwd, int prec) {
+  const bool f16 = prec == kPrecF16;
+  switch (v) {
+    case kGruF32:
+      return {bwd ? kp(gru_bwd_persistent_kernel<H>) : kp(gru_fwd_persistent_kernel<H>), 256,
+              lds_bytes(H, bwd, kPrecF32), ""};
+    case kGruDc:
+    case kGruDcFused:
+      return {bwd                 ? kp(gru_bwd_persistent_dc_kernel<H>)
+              : v == kGruDcFused ? kp(gru_fwd_persistent_dc_kernel<H, true>)
+                                 : kp(gru_fwd_persistent_dc_kernel<H, false>),
+              512, (bwd ? dc_bwd_lds_floats(H) : dc_fwd_lds_floats(H)) * 4, "_dc"};
+    case kGruLp:
+      return {bwd ? (f16 ? kp(gru_bwd_persistent_lp_kernel<H, true>) : kp(gru_bwd_persistent_lp_kernel<H, false>))
+                  : (f16 ? kp(gru_fwd_persistent_lp_kernel<H, true>) : kp(gru_fwd_persistent_lp_kernel<H, false>)),
+              256, lds_bytes(H, bwd, prec), "_lp"};
+    case kGruLp2:
+      return {bwd ? (f16 ? kp(gru_bwd_persistent_lp2_kernel<H, true, 2>) : kp(gru_bwd_persistent_lp2_kernel<H, false, 2>))
+                  : (f16 ? kp(gru_fwd_persistent_lp2_kernel<H, true, 2>) : kp(gru_fwd_persistent_lp2_kernel<H, false, 2>)),
+              256, lp2_lds_bytes(H, bwd, 2), "_lp2"};
+    case kGruLp2Wide:
+      return {bwd ? (f16 ? kp(gru_bwd_persistent_lp2_kernel<H, true, 4>) : kp(gru_bwd_persistent_lp2_kernel<H, false, 4>))
+                  : (f16 ? kp(gru_fwd_persistent_lp2_kernel<H, true, 4>) : kp(gru_fwd_persistent_lp2_kernel<H, false, 4>)),
+              512, lp2_lds_bytes(H, bwd, 4), "_lp2w"};
+    case kGruLp2Dw:   // backward only
+      return {f16 ? kp(gru_bwd_persistent_lp2_kernel<H, true, 2, true>) : kp(gru_bwd_persistent_lp2_kernel<H, false, 2, true>),
+              512, lp2_lds_bytes(H, true, 2, true), "_lp2dw"};
+    case kGruLp2Ow:   // forward only
+      return {f16 ? kp(gru_fwd_persistent_lp2_kernel<H, true, 2, true>) : kp(gru_fwd_persistent_lp2_kernel<H, false, 2, true>),
+              512, lp2_lds_bytes(H, false, 2, false, true), "_lp2ow"};
+    default:
+      return {nullptr, 0, 0, ""};
   }
-  if (prec == kPrecF16)
-    return backward ? reinterpret_cast<const void*>(gru_bwd_persistent_lp2_kernel<H, true, 2>)
-                    : reinterpret_cast<const void*>(gru_fwd_persistent_lp2_kernel<H, true, 2>);
-  return backward ? reinterpret_cast<const void*>(gru_bwd_persistent_lp2_kernel<H, false, 2>)
-                  : reinterpret_cast<const void*>(gru_fwd_persistent_lp2_kernel<H, false, 2>);
 }
 
-template <int H>
-const void* lp2_dw_kernel_ptr(int prec) {
-  return prec == kPrecF16 ? reinterpret_cast<const void*>(gru_bwd_persistent_lp2_kernel<H, true, 2, true>)
-                          : reinterpret_cast<const void*>(gru_bwd_persistent_lp2_kernel<H, false, 2, true>);
-}
-
-template <int H>
-const void* lp2_ow_kernel_ptr(int prec) {
-  return prec == kPrecF16 ? reinterpret_cast<const void*>(gru_fwd_persistent_lp2_kernel<H, true, 2, true>)
-                          : reinterpret_cast<const void*>(gru_fwd_persistent_lp2_kernel<H, false, 2, true>);
-}
-
-template <int H>
-int lp2_ow_occupancy_ok(int prec) {
+// Workgroups of one kernel resident per CU at its launch shape: asked once per kernel and process (the query also
+// raises the kernel's dynamic-LDS limit, which its launch needs).  The two rules the kernels came with are kept:
+// soft (the fused-dW_hh and worker-wave kernels, the largest LDS users): LDS beyond the CU's 160 KB or a refused
+// hipFuncSetAttribute is the answer "does not fit" (0, cached); otherwise such a failure is an error, nothing is
+// cached and the next call asks again.
+int kernel_occupancy(const RecKernel& k, bool soft, int* occ) {
   static std::mutex mu;
-  static int occ[3] = {-1, -1, -1};
+  static std::map<const void*, int> cache;
   std::lock_guard<std::mutex> lk(mu);
-  int& o = occ[prec];
-  if (o < 0) {
-    const void* k = lp2_ow_kernel_ptr<H>(prec);
-    const size_t lds = lp2_lds_bytes(H, false, 2, false, true);
-    o = 0;
-    if (lds <= 160 * 1024 && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess)
-      SRK_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k, 512, lds));
+  const auto it = cache.find(k.fn);
+  if (it != cache.end()) {
+    *occ = it->second;
+    return SRK_OK;
+  }
+  if (soft) {
+    int& o = cache[k.fn] = 0;
+    *occ = 0;
+    if (k.lds <= 160 * 1024 &&
+        hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds) == hipSuccess)
+      SRK_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k.fn, k.block, k.lds));
     (void)hipGetLastError();
+    *occ = o;
+    return SRK_OK;
   }
-  return o >= 1 ? 1 : 0;
+  int o = -1;
+  SRK_CHECK_HIP(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds));
+  SRK_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k.fn, k.block, k.lds));
+  *occ = cache[k.fn] = o;
+  return SRK_OK;
 }
 
-template <int H>
-int lp2_dw_occupancy_ok(int prec) {
+int device_cus(int* cus) {
   static std::mutex mu;
-  static int occ[3] = {-1, -1, -1};
+  static int n = -1;
   std::lock_guard<std::mutex> lk(mu);
-  int& o = occ[prec];
-  if (o < 0) {
-    const void* k = lp2_dw_kernel_ptr<H>(prec);
-    const size_t lds = lp2_lds_bytes(H, true, 2, true);
-    o = 0;
-    if (lds <= 160 * 1024 && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess)
-      SRK_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k, 512, lds));
-    (void)hipGetLastError();
-  }
-  return o >= 1 ? 1 : 0;
-}
-
-template <int H>
-int lp2_occupancy_ok(bool backward, int prec, int RB = 2) {
-  static std::mutex mu;
-  static int occ[2][2][3] = {{{-1, -1, -1}, {-1, -1, -1}}, {{-1, -1, -1}, {-1, -1, -1}}};
-  std::lock_guard<std::mutex> lk(mu);
-  int& o = occ[RB == 4 ? 1 : 0][backward ? 1 : 0][prec];
-  if (o < 0) {
-    const void* k = lp2_kernel_ptr<H>(backward, prec, RB);
-    const size_t lds = lp2_lds_bytes(H, backward, RB);
-    SRK_CHECK_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SRK_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k, 128 * RB, lds));
-  }
-  return o >= 1 ? 1 : 0;
-}
-
-template <int H>
-const void* kernel_ptr(bool backward, int prec) {
-  if (prec == kPrecBF16)
-    return backward ? reinterpret_cast<const void*>(gru_bwd_persistent_lp_kernel<H, false>)
-                    : reinterpret_cast<const void*>(gru_fwd_persistent_lp_kernel<H, false>);
-  if (prec == kPrecF16)
-    return backward ? reinterpret_cast<const void*>(gru_bwd_persistent_lp_kernel<H, true>)
-                    : reinterpret_cast<const void*>(gru_fwd_persistent_lp_kernel<H, true>);
-  return backward ? reinterpret_cast<const void*>(gru_bwd_persistent_kernel<H>)
-                  : reinterpret_cast<const void*>(gru_fwd_persistent_kernel<H>);
-}
-
-template <int H>
-int dc_occupancy_ok() {
-  static std::mutex mu;
-  static int occ = -1;
-  std::lock_guard<std::mutex> lk(mu);
-  if (occ < 0) {
-    int o2 = 0;
-    const std::pair<const void*, size_t> ks[3] = {
-        {reinterpret_cast<const void*>(gru_fwd_persistent_dc_kernel<H, false>), dc_fwd_lds_floats(H) * 4},
-        {reinterpret_cast<const void*>(gru_fwd_persistent_dc_kernel<H, true>), dc_fwd_lds_floats(H) * 4},
-        {reinterpret_cast<const void*>(gru_bwd_persistent_dc_kernel<H>), dc_bwd_lds_floats(H) * 4}};
-    for (const auto& k : ks) {
-      SRK_CHECK_HIP(hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.second));
-      SRK_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o2, k.first, 512, k.second));
-      occ = occ < 0 ? o2 : std::min(occ, o2);
-    }
-  }
-  return occ >= 1 ? 1 : 0;
-}
-
-template <int H>
-int occupancy_ok(bool backward, int prec, int grid) {
-  static std::mutex mu;
-  static int cus = -1, occ[2][3] = {{-1, -1, -1}, {-1, -1, -1}};
-  std::lock_guard<std::mutex> lk(mu);
-  if (cus < 0) {
+  if (n < 0) {
     int dev = 0;
     SRK_CHECK_HIP(hipGetDevice(&dev));
     hipDeviceProp_t p;
     SRK_CHECK_HIP(hipGetDeviceProperties(&p, dev));
-    cus = p.multiProcessorCount;
+    n = p.multiProcessorCount;
   }
-  int& o = occ[backward ? 1 : 0][prec];
-  if (o < 0) {
-    const void* k = kernel_ptr<H>(backward, prec);
-    const size_t lds = lds_bytes(H, backward, prec);
-    SRK_CHECK_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SRK_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k, 256, lds));
-  }
-  return (o >= 1 && grid <= cus) ? 1 : 0;   // one workgroup per CU: the sc1 hand-off form measured
+  *cus = n;
+  return SRK_OK;
 }
 
 }  // namespace
@@ -2355,43 +2317,77 @@ int occupancy_ok(bool backward, int prec, int grid) {
 size_t fwd_lds_bytes(int H) { return (size_t)(3 * 16 * (H + 4) + 64 * 20 + 48 * kXP) * 4; }
 size_t bwd_lds_bytes(int H) { return (size_t)(16 * (3 * H + 4) + 64 * 4 * 20) * 4; }
 
-int gru_persistent_groups(int64_t H) {
-  if (H != 512) return 0;
-  return 4;   // 2 dirs x 4 groups x 32 slices = 256 workgroups (one per CU)
+GruOpts gru_opts() {
+  return {g_opt_gru_persistent, g_opt_gru_lp2, g_opt_gru_lp_wide, g_opt_gru_dc, g_opt_gru_fast_cell,
+          g_opt_gru_dwhh_fused, g_opt_gru_fwd_worker};
 }
 
-int gru_persistent_supported(int64_t B, int64_t T, int64_t H, bool backward) {
-  const int gmax = gru_persistent_groups(H);
-  if (gmax == 0) return 0;
-  // byte offsets of the buffer instructions are 32-bit
-  if ((double)B * T * 3 * H * 4 >= 2147483647.0 || (double)B * T * 2 * H * 4 >= 2147483647.0) return 0;
-  const int64_t G = std::min<int64_t>((B + kRows - 1) / kRows, gmax);
-  const int grid = (int)(2 * G * (H / kUnits));
-  const int prec = matmul_prec();
-  int ok = occupancy_ok<512>(backward, prec, grid);
-  if (ok > 0 && prec != kPrecF32 && g_opt_gru_lp2) ok = lp2_occupancy_ok<512>(backward, prec);
-  return ok < 0 ? 0 : ok;
+// > 0: fits; 0: does not; < 0: the query failed (srk_last_error says how) — the plan takes that as "does not fit".
+int gru_fit_measured(GruVariant v, int prec, bool backward, int grid) {
+  int occ = 0, cus = 0;
+  if (v == kGruDc || v == kGruDcFused) {   // the two-chain kernels run as a family: all three must fit
+    const std::pair<GruVariant, bool> ks[3] = {{kGruDc, false}, {kGruDcFused, false}, {kGruDc, true}};
+    int all = 1;
+    for (const auto& k : ks) {
+      if (int rc = kernel_occupancy(rec_kernel<512>(k.first, k.second, prec), false, &occ)) return rc;
+      all = std::min(all, occ);
+    }
+    return all >= 1 ? 1 : 0;
+  }
+  const bool base = v == kGruF32 || v == kGruLp;   // one workgroup per CU: the sc1 hand-off form measured
+  if (base)
+    if (int rc = device_cus(&cus)) return rc;
+  if (int rc = kernel_occupancy(rec_kernel<512>(v, backward, prec), v == kGruLp2Dw || v == kGruLp2Ow, &occ)) return rc;
+  return (occ >= 1 && (!base || grid <= cus)) ? 1 : 0;
 }
 
-// 16-bit recurrence over more than 256 rows: the 64-row workgroups (RB = 4) run up to 512 rows per
-// launch instead of 256-row chunks one after the other (a fused input projection needs in <= 40)
-bool lp2_wide(int64_t B, int prec, bool backward, int in_fused) {
-  return prec != kPrecF32 && g_opt_gru_lp2 && g_opt_gru_lp_wide && B > 256 && in_fused <= 40 &&
-         lp2_occupancy_ok<512>(backward, prec, 4) > 0;
+GruRecPlan gru_rec_plan(int64_t B, int64_t T, int64_t H, int in_fused, int prec, bool backward, bool out16,
+                        const GruOpts& o, GruFitFn fits) {
+  GruRecPlan p;
+  p.prec = prec;
+  const bool f32 = prec == kPrecF32;
+  // Can the persistent kernels run this layer at all?  H; the byte offsets of the buffer instructions are 32-bit;
+  // the base kernel's grid (2 dirs x <= 4 groups x 32 slices = 256 workgroups, one per CU) co-resident; and the
+  // 32 x 32 kernel, where the options select it, fitting a CU.
+  if (!o.persistent || H != 512) return p;
+  if ((double)B * T * 3 * H * 4 >= 2147483647.0 || (double)B * T * 2 * H * 4 >= 2147483647.0) return p;
+  const int64_t G = std::min<int64_t>((B + kRows - 1) / kRows, 4);
+  if (fits(f32 ? kGruF32 : kGruLp, prec, backward, (int)(2 * G * (H / kUnits))) <= 0) return p;
+  if (!f32 && o.lp2 && fits(kGruLp2, prec, backward, 0) <= 0) return p;
+  // Which one.  The 16-bit backward kernels on 32 x 32 workgroups write the 16-bit outputs only.
+  const bool lp2 = !f32 && o.lp2 && (!backward || out16);
+  if (f32) {
+    const bool dc = o.dc && fits(kGruDc, prec, backward, 0) > 0;   // two-chain 8-wave kernels (same grid, W slice, outputs)
+    p.variant = !dc ? kGruF32 : (!backward && in_fused) ? kGruDcFused : kGruDc;
+    p.fast_cell = dc && o.fast_cell;
+  } else if (!lp2) {
+    p.variant = kGruLp;
+  } else if (o.lp_wide && B > 256 && in_fused <= 40 && fits(kGruLp2Wide, prec, backward, 0) > 0) {
+    // more than 256 rows: the 64-row workgroups (RB = 4) run up to 512 rows per launch instead of 256-row chunks
+    // one after the other (a fused input projection needs in <= 40)
+    p.variant = kGruLp2Wide;
+  } else if (backward && o.dwhh_fused && T >= 2 && fits(kGruLp2Dw, prec, true, 0) > 0) {
+    p.variant = kGruLp2Dw;
+  } else if (!backward && o.fwd_worker && out16 && (double)2 * T * B * 4 * H * 4 < 2147483647.0 &&
+             fits(kGruLp2Ow, prec, false, 0) > 0) {
+    p.variant = kGruLp2Ow;   // (the gate store offsets are 32-bit buffer offsets)
+  } else {
+    p.variant = kGruLp2;
+  }
+  const RecKernel k = rec_kernel<512>(p.variant, backward, prec);
+  p.kernel = k.fn;
+  p.block = k.block;
+  p.lds = k.lds;
+  p.suffix = k.suffix;
+  const bool wide = p.variant == kGruLp2Wide, ww32 = p.variant >= kGruLp2;   // 32-unit slices
+  p.rows_per_launch = wide ? 512 : 4 * kRows;
+  p.rows_g = wide ? 64 : ww32 ? kRows2 : kRows;
+  p.slices = (int)(ww32 ? H / kUnits2 : H / kUnits);
+  p.bias_part_rows = p.rows_g;   // one partial per row group
+  p.dw_parts = p.variant == kGruLp2Dw ? (int)((B + 255) / 256) * 8 : 0;
+  return p;
 }
 
-int gru_dwhh_fused_parts(int64_t B, int64_t T) {
-  const int prec = matmul_prec();
-  if (!g_opt_gru_dwhh_fused || prec == kPrecF32 || !g_opt_gru_lp2 || T < 2 || lp2_wide(B, prec, true, 0)) return 0;
-  if (lp2_dw_occupancy_ok<512>(prec) <= 0) return 0;
-  return (int)((B + 255) / 256) * 8;
-}
-
-int gru_bias_part_rows(int64_t B) {
-  const int prec = matmul_prec();
-  if (lp2_wide(B, prec, true, 0)) return 64;
-  return (prec != kPrecF32 && g_opt_gru_lp2) ? kRows2 : kRows;
-}
 
 // Zeroes the kCounterFloats flag / counter words before a launch.  A kernel, not hipMemsetAsync: as a
 // memset node of a captured HIP graph the clear was not reliably visible to the agent-scope flag loads
@@ -2402,26 +2398,17 @@ __global__ void __launch_bounds__(256) zero_counters_kernel(unsigned* __restrict
   if (i < n) __hip_atomic_store(p + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-int gru_fp32_fast_cell() { return g_opt_gru_fast_cell && g_opt_gru_dc && dc_occupancy_ok<512>() > 0; }
-
-int gru_persistent_launch(GruPArgs a, bool backward, hipStream_t s) {
-  const int gmax = gru_persistent_groups(a.H);
-  SRK_REQUIRE(gmax > 0 && a.H == 512, SRK_ERR_INVALID, "gru persistent: unsupported H");
-  const int prec = matmul_prec();
-  SRK_REQUIRE(!a.one_dir || prec == kPrecF32, SRK_ERR_INVALID, "gru persistent: one_dir is an fp32 mode");
-  const bool wide = lp2_wide(a.B, prec, backward, a.x_in ? a.in : 0) && (!backward || a.dgi16 != nullptr);
-  const int rows_per_launch = wide ? 512 : gmax * kRows;
-  // 16-bit operands: the 32 x 32 workgroup kernels (the backward one writes the 16-bit outputs only)
-  const bool lp2 = prec != kPrecF32 && g_opt_gru_lp2 && (!backward || a.dgi16 != nullptr);
-  const int rows_g = wide ? 64 : lp2 ? kRows2 : kRows, slices = lp2 ? a.H / kUnits2 : a.H / kUnits;
-  if (lp2 && lp2_occupancy_ok<512>(backward, prec) <= 0)
-    SRK_REQUIRE(false, SRK_ERR_INVALID, "gru persistent: the 32 x 32 kernels do not fit one workgroup per CU");
-  // fp32 forward: the two-chain 8-wave kernel (same grid, W slice and outputs)
-  const bool dc = prec == kPrecF32 && g_opt_gru_dc && dc_occupancy_ok<512>() > 0;
-  // 16-bit forward on 32-row workgroups: the output / input worker waves (option gru_fwd_worker; the gate
-  // store offsets are 32-bit buffer offsets)
-  const bool ow = lp2 && !backward && !wide && g_opt_gru_fwd_worker && a.y16 &&
-                  (double)2 * a.T * a.B * 4 * a.H * 4 < 2147483647.0 && lp2_ow_occupancy_ok<512>(prec) > 0;
+int gru_persistent_launch(GruPArgs a, const GruRecPlan& plan, bool backward, hipStream_t s) {
+  SRK_REQUIRE(plan.variant != kGruStep && a.H == 512, SRK_ERR_INVALID,
+              "gru persistent: no persistent kernel runs this layer (H, co-residency, one workgroup per CU)");
+  const bool f32 = plan.prec == kPrecF32;
+  SRK_REQUIRE(!a.one_dir || f32, SRK_ERR_INVALID, "gru persistent: one_dir is an fp32 mode");
+  SRK_REQUIRE(plan.variant != kGruLp2Dw || (a.dw_part && a.y16_in), SRK_ERR_INTERNAL,
+              "gru persistent: fused dW_hh needs its partials and y16");
+  const bool dc_fwd = !backward && (plan.variant == kGruDc || plan.variant == kGruDcFused);
+  SRK_REQUIRE(!dc_fwd || (plan.variant == kGruDcFused) == (a.x_in != nullptr), SRK_ERR_INTERNAL,
+              "gru persistent: the plan's fused projection and x_in disagree");
+  const int rows_per_launch = plan.rows_per_launch;
   for (int c0 = 0; c0 < a.B; c0 += rows_per_launch) {
     GruPArgs ac = a;
     ac.trace = g_opt_gru_trace;
@@ -2437,36 +2424,18 @@ int gru_persistent_launch(GruPArgs a, bool backward, hipStream_t s) {
     ac.dw_mode = g_opt_gru_dwhh_fused;
     ac.b_begin = c0;
     ac.b_end = std::min(a.B, c0 + rows_per_launch);
-    ac.G = (ac.b_end - c0 + rows_g - 1) / rows_g;
+    ac.G = (ac.b_end - c0 + plan.rows_g - 1) / plan.rows_g;
     ac.chunk = c0 / rows_per_launch;
     hipLaunchKernelGGL(zero_counters_kernel, dim3((kCounterFloats + 255) / 256), dim3(256), 0, s, ac.counters,
                        (int)kCounterFloats);
-    const dim3 grid((unsigned)(2 * ac.G * slices));
+    const dim3 grid((unsigned)(2 * ac.G * plan.slices));
     const double flops = 2.0 * (a.one_dir ? 1.0 : 2.0) * (double)(ac.b_end - c0) * 3 * a.H * a.H * (a.T - 1);
-    ProfScope prof(backward ? (prec == kPrecF32 ? "gru_bwd_seq" : "gru_bwd_seq_lp")
-                            : (prec == kPrecF32 ? "gru_fwd_seq" : "gru_fwd_seq_lp"), s, flops);
-    prof.detail("gru_%s_persistent%s_kernel B%d T%d chunk%d", backward ? "bwd" : "fwd",
-                dc ? "_dc" : wide ? "_lp2w" : lp2 ? (backward && ac.dw_part ? "_lp2dw" : ow ? "_lp2ow" : "_lp2") : (prec == kPrecF32 ? "" : "_lp"),
-                ac.b_end - c0, a.T, ac.chunk);
-    if (dc && backward)
-      hipLaunchKernelGGL((gru_bwd_persistent_dc_kernel<512>), grid, dim3(512), dc_bwd_lds_floats(512) * 4, s, ac);
-    else if (dc && ac.x_in)
-      hipLaunchKernelGGL((gru_fwd_persistent_dc_kernel<512, true>), grid, dim3(512), dc_fwd_lds_floats(512) * 4, s, ac);
-    else if (dc)
-      hipLaunchKernelGGL((gru_fwd_persistent_dc_kernel<512, false>), grid, dim3(512), dc_fwd_lds_floats(512) * 4, s, ac);
-    else if (lp2 && backward && ac.dw_part) {   // with the fused recurrent weight gradient (gru_dwhh_fused_parts)
-      SRK_REQUIRE(!wide && ac.y16_in, SRK_ERR_INTERNAL, "gru persistent: fused dW_hh needs the 32-row kernel and y16");
-      hipLaunchKernelGGL(reinterpret_cast<void (*)(GruPArgs)>(const_cast<void*>(lp2_dw_kernel_ptr<512>(prec))), grid,
-                         dim3(512), lp2_lds_bytes(512, true, 2, true), s, ac);
-    } else if (lp2 && !backward && ow) {   // the forward with the output / input worker waves
-      hipLaunchKernelGGL(reinterpret_cast<void (*)(GruPArgs)>(const_cast<void*>(lp2_ow_kernel_ptr<512>(prec))), grid,
-                         dim3(512), lp2_lds_bytes(512, false, 2, false, true), s, ac);
-    } else if (lp2)
-      hipLaunchKernelGGL(reinterpret_cast<void (*)(GruPArgs)>(const_cast<void*>(lp2_kernel_ptr<512>(backward, prec, wide ? 4 : 2))),
-                         grid, dim3(wide ? 512 : 256), lp2_lds_bytes(512, backward, wide ? 4 : 2), s, ac);
-    else
-      hipLaunchKernelGGL(reinterpret_cast<void (*)(GruPArgs)>(const_cast<void*>(kernel_ptr<512>(backward, prec))), grid,
-                         dim3(256), lds_bytes(512, backward, prec), s, ac);
+    ProfScope prof(backward ? (f32 ? "gru_bwd_seq" : "gru_bwd_seq_lp") : (f32 ? "gru_fwd_seq" : "gru_fwd_seq_lp"), s,
+                   flops);
+    prof.detail("gru_%s_persistent%s_kernel B%d T%d chunk%d", backward ? "bwd" : "fwd", plan.suffix, ac.b_end - c0,
+                a.T, ac.chunk);
+    hipLaunchKernelGGL(reinterpret_cast<void (*)(GruPArgs)>(const_cast<void*>(plan.kernel)), grid, dim3(plan.block),
+                       plan.lds, s, ac);
     SRK_CHECK_HIP(hipGetLastError());
   }
   return SRK_OK;
@@ -2525,10 +2494,10 @@ extern "C" int64_t srk_spin_timeouts(void) {
   return (int64_t)v;
 }
 
-// Host-side audit of the step-ordering words (tests/test_gru_audit.py, no GPU needed): plans the
-// launches of gru_persistent_launch for a batch of B rows (256-row chunks, the variant the current
-// options and precision select) and walks every word each workgroup polls, stores or adds to with
-// the kernels' own index helpers.  *max_word = the largest word touched (must stay below the census
+// Host-side audit of the step-ordering words (tests/test_gru_audit.py, no GPU needed): takes the plan
+// gru_persistent_launch runs for a batch of B rows (gru_rec_plan: the variant the current options and
+// precision select, its chunks and row groups) and walks every word each workgroup polls, stores or
+// adds to with the kernels' own index helpers.  *max_word = the largest word touched (must stay below the census
 // at kCensusOff), *chunks = launches, *census = kCensusOff.  A fault that depends on the chunk
 // (b_begin > 0) would need a chunk-dependent word: none of these indices involves b_begin.
 extern "C" int srk_gru_audit_words(int64_t B, int precision, int backward, int64_t* max_word, int64_t* chunks,
@@ -2537,11 +2506,15 @@ extern "C" int srk_gru_audit_words(int64_t B, int precision, int backward, int64
   SRK_REQUIRE(B > 0 && max_word && chunks && census && precision >= 0 && precision <= 2, SRK_ERR_INVALID,
               "gru_audit_words: bad arguments");
   using namespace srk;
-  const bool lp2 = precision != kPrecF32 && g_opt_gru_lp2;
-  const bool wide = lp2 && g_opt_gru_lp_wide && B > 256;   // as lp2_wide (occupancy aside)
-  const int rows_per_launch = wide ? 512 : gru_persistent_groups(512) * kRows;
-  const bool dc = precision == kPrecF32 && g_opt_gru_dc;
-  const int rows_g = wide ? 64 : lp2 ? kRows2 : kRows, S = lp2 ? 512 / kUnits2 : 512 / kUnits;
+  // the plan of a T = 1 layer with its 16-bit outputs, the persistent path on and every kernel fitting (no device);
+  // its chunking depends on B only through B > 256, so any B is audited, also one past the 32-bit offsets
+  GruOpts o = gru_opts();
+  o.persistent = 1;
+  const GruRecPlan plan = gru_rec_plan(std::min<int64_t>(B, 512), 1, 512, 0, precision, backward != 0, true, o,
+                                       [](GruVariant, int, bool, int) { return 1; });
+  SRK_REQUIRE(plan.variant != kGruStep, SRK_ERR_INTERNAL, "gru_audit_words: no plan");
+  const bool dc = plan.variant == kGruDc || plan.variant == kGruDcFused, lp2 = plan.variant >= kGruLp2;
+  const int rows_per_launch = plan.rows_per_launch, rows_g = plan.rows_g, S = plan.slices;
   int64_t mx = -1, n = 0;
   auto see = [&](int w) { mx = std::max<int64_t>(mx, w); };
   for (int64_t c0 = 0; c0 < B; c0 += rows_per_launch, ++n) {
@@ -2566,8 +2539,7 @@ extern "C" int srk_gru_audit_words(int64_t B, int precision, int backward, int64
         }
       }
   }
-  (void)backward;   // the backward kernels use the same words as their forward twins
-  *max_word = mx;
+  *max_word = mx;   // (the backward kernels use the same words as their forward twins)
   *chunks = n;
   *census = kCensusOff;
   return SRK_OK;

@@ -82,129 +82,113 @@ class _GRULayerFn(torch.autograd.Function):
     pairs (weight_ih_lN, weight_ih_lN_reverse), ... of the parameters themselves."""
 
     @staticmethod
-    def forward(ctx, x, grad_on, w_ih_f, w_ih_r, w_hh_f, w_hh_r, b_ih_f, b_ih_r, b_hh_f, b_hh_r):
-        # grad_on: torch.is_grad_enabled() at the call (inside forward it is always off, and
-        # needs_input_grad ignores it): an evaluation pass under no_grad must not register copies
-        B, T, IN = x.shape
-        H = w_hh_f.shape[-1]
-        x = x.contiguous()
-        w_ih, w_hh = _dir_pair(w_ih_f, w_ih_r), _dir_pair(w_hh_f, w_hh_r)
-        b_ih, b_hh = _dir_pair(b_ih_f, b_ih_r), _dir_pair(b_hh_f, b_hh_r)
-        _check_cuda(x, w_ih, w_hh, b_ih, b_hh)
-        y = torch.empty((B, T, 2 * H), device=x.device, dtype=torch.float32)
-        ws = torch.empty(int(_lib.lib().srk_gru_workspace_floats(B, T, IN, H, 0)), device=x.device)
-        # 16-bit modes: the previous layer's own 16-bit copy of h is this layer's x16 (module note at
-        # _copies16); this layer's copy of its output goes to the next layer
-        x16 = _copy16_get(x) if IN % 8 == 0 else None
-        call("srk_gru_layer_fwd_x16", ptr(x), _optr(x16), B, T, IN, H, ptr(w_ih),
-             ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(y), ptr(ws), stream_ptr())
-        ctx.x16 = x16
+    def forward(ctx, x, grad_on, *params):
+        (B, T, IN, H), x, pairs, y, ws, x16 = _gru_operands(x, params, "srk_gru_workspace_floats")
+        call("srk_gru_layer_fwd_x16", ptr(x), _optr(x16), B, T, IN, H, *map(ptr, pairs), ptr(y), ptr(ws), stream_ptr())
+        # this layer's 16-bit copy of its output goes to the next layer
         off = int(_lib.lib().srk_gru_y16_offset(B, T, IN, H)) if _copy16_wanted(2 * H) else -1
         if off >= 0 and grad_on and any(ctx.needs_input_grad):
             _copy16_put(y, ws[off:].view(torch.int16)[:y.numel()])
-        ctx.save_for_backward(x, w_ih, w_hh, y, ws)
-        ctx.dims = (B, T, IN, H)
-        ctx.params = (w_ih_f, w_ih_r, w_hh_f, w_hh_r, b_ih_f, b_ih_r, b_hh_f, b_hh_r)
-        ctx.prec = _lib.matmul_precision()   # the backward runs at its forward's precision
-        red = _reducer_of(w_ih_f)
-        if red is not None and grad_on and any(ctx.needs_input_grad):
-            red.persistent_pending(1)      # collectives wait until this layer's recurrence is enqueued
+        _gru_forward_done(ctx, grad_on, (B, T, IN, H), x, pairs, y, ws, x16, params)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, w_ih, w_hh, y, ws = ctx.saved_tensors
-        B, T, IN, H = ctx.dims
-        P = ctx.params
-        dy = dy.contiguous()
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        targets = [_grad_pair(P[2 * i], P[2 * i + 1]) for i in range(4)]
-        acc = all(t is not None for t in targets) and all(ctx.needs_input_grad[2:])
-        if acc:   # accumulate straight into the parameters' .grad (FlatParams)
-            dw_ih, dw_hh, db_ih, db_hh = targets
-        else:
-            dw_ih, dw_hh = torch.empty_like(w_ih), torch.empty_like(w_hh)
-            db_ih = torch.empty((2, 3 * H), device=x.device)
-            db_hh = torch.empty((2, 3 * H), device=x.device)
-        ws2 = torch.empty(int(_lib.lib().srk_gru_workspace_floats(B, T, IN, H, 1)), device=x.device)
+        (x, w_ih, w_hh, y, ws), (B, T, IN, H), dx, grads, acc, ws2 = _gru_backward_buffers(
+            ctx, "srk_gru_workspace_floats")
         _copy16_drop(y)   # the next layer's backward has run
+        dy = dy.contiguous()
         x16, ctx.x16 = ctx.x16, None
         with _lib.precision_scope(ctx.prec):
-            call("srk_gru_layer_bwd_x16", ptr(x), _optr(x16), B, T, IN, H, ptr(w_ih),
-                 ptr(w_hh), ptr(y), ptr(ws), ptr(dy), _optr(dx), ptr(dw_ih), ptr(dw_hh),
-                 ptr(db_ih), ptr(db_hh), int(acc), ptr(ws2), stream_ptr())
-        red = _reducer_of(P[0])
-        if red is not None:
-            red.persistent_done()
-            if acc:
-                red.mark_ready(P)
-        if acc:
-            return (dx, None) + (None,) * 8
-        return (dx, None, dw_ih[0], dw_ih[1], dw_hh[0], dw_hh[1], db_ih[0], db_ih[1], db_hh[0], db_hh[1])
+            call("srk_gru_layer_bwd_x16", ptr(x), _optr(x16), B, T, IN, H, ptr(w_ih), ptr(w_hh), ptr(y), ptr(ws),
+                 ptr(dy), _optr(dx), *map(ptr, grads), int(acc), ptr(ws2), stream_ptr())
+        return _gru_backward_done(ctx, dx, grads, acc)
 
 
 class _GRUTopLastFn(torch.autograd.Function):
     """The top BiGRU layer of a model that reads only the last step (srk_gru_top_last_fwd / _bwd): returns row T-1
-    of the layer, [B, 2H], and takes dy_last [B, 2H] in backward.  Everything around the kernels is _GRULayerFn's:
-    grad_on, the in-place accumulation into FlatParams grads, the reducer hand-shake, the backward at its forward's
-    precision.  The full y is kept for the backward only and never returned (in the library's modes 2 and 3 its
-    reverse half is unwritten below the last step)."""
+    of the layer, [B, 2H], and takes dy_last [B, 2H] in backward.  Everything around the kernels is _GRULayerFn's
+    (the _gru_* helpers below).  The full y is kept for the backward only and never returned (in the library's
+    modes 2 and 3 its reverse half is unwritten below the last step)."""
 
     @staticmethod
-    def forward(ctx, x, grad_on, w_ih_f, w_ih_r, w_hh_f, w_hh_r, b_ih_f, b_ih_r, b_hh_f, b_hh_r):
-        B, T, IN = x.shape
-        H = w_hh_f.shape[-1]
-        x = x.contiguous()
-        w_ih, w_hh = _dir_pair(w_ih_f, w_ih_r), _dir_pair(w_hh_f, w_hh_r)
-        b_ih, b_hh = _dir_pair(b_ih_f, b_ih_r), _dir_pair(b_hh_f, b_hh_r)
-        _check_cuda(x, w_ih, w_hh, b_ih, b_hh)
-        y = torch.empty((B, T, 2 * H), device=x.device, dtype=torch.float32)
+    def forward(ctx, x, grad_on, *params):
+        (B, T, IN, H), x, pairs, y, ws, x16 = _gru_operands(x, params, "srk_gru_top_last_workspace_floats")
         y_last = torch.empty((B, 2 * H), device=x.device, dtype=torch.float32)
-        ws = torch.empty(int(_lib.lib().srk_gru_top_last_workspace_floats(B, T, IN, H, 0)), device=x.device)
-        x16 = _copy16_get(x) if IN % 8 == 0 else None   # the layer below's 16-bit copy of its h (16-bit modes)
         mode = ctypes.c_int(0)
-        call("srk_gru_top_last_fwd", ptr(x), _optr(x16), B, T, IN, H, ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh),
-             ptr(y), ptr(y_last), ptr(ws), ctypes.byref(mode), stream_ptr())
-        ctx.x16 = x16
+        call("srk_gru_top_last_fwd", ptr(x), _optr(x16), B, T, IN, H, *map(ptr, pairs), ptr(y), ptr(y_last), ptr(ws),
+             ctypes.byref(mode), stream_ptr())
         ctx.mode = mode.value
-        ctx.save_for_backward(x, w_ih, w_hh, y, ws)
-        ctx.dims = (B, T, IN, H)
-        ctx.params = (w_ih_f, w_ih_r, w_hh_f, w_hh_r, b_ih_f, b_ih_r, b_hh_f, b_hh_r)
-        ctx.prec = _lib.matmul_precision()
-        red = _reducer_of(w_ih_f)
-        if red is not None and grad_on and any(ctx.needs_input_grad):
-            red.persistent_pending(1)
+        _gru_forward_done(ctx, grad_on, (B, T, IN, H), x, pairs, y, ws, x16, params)
         return y_last
 
     @staticmethod
     def backward(ctx, dy_last):
-        x, w_ih, w_hh, y, ws = ctx.saved_tensors
-        B, T, IN, H = ctx.dims
-        P = ctx.params
+        (x, w_ih, w_hh, y, ws), (B, T, IN, H), dx, grads, acc, ws2 = _gru_backward_buffers(
+            ctx, "srk_gru_top_last_workspace_floats")
         dy_last = dy_last.contiguous()
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        targets = [_grad_pair(P[2 * i], P[2 * i + 1]) for i in range(4)]
-        acc = all(t is not None for t in targets) and all(ctx.needs_input_grad[2:])
-        if acc:
-            dw_ih, dw_hh, db_ih, db_hh = targets
-        else:
-            dw_ih, dw_hh = torch.empty_like(w_ih), torch.empty_like(w_hh)
-            db_ih = torch.empty((2, 3 * H), device=x.device)
-            db_hh = torch.empty((2, 3 * H), device=x.device)
-        ws2 = torch.empty(int(_lib.lib().srk_gru_top_last_workspace_floats(B, T, IN, H, 1)), device=x.device)
         x16, ctx.x16 = ctx.x16, None
         with _lib.precision_scope(ctx.prec):
             call("srk_gru_top_last_bwd", ptr(x), _optr(x16), B, T, IN, H, ptr(w_ih), ptr(w_hh), ptr(y), ptr(ws),
-                 ptr(dy_last), ctx.mode, _optr(dx), ptr(dw_ih), ptr(dw_hh), ptr(db_ih), ptr(db_hh), int(acc), ptr(ws2),
-                 stream_ptr())
-        red = _reducer_of(P[0])
-        if red is not None:
-            red.persistent_done()
-            if acc:
-                red.mark_ready(P)
+                 ptr(dy_last), ctx.mode, _optr(dx), *map(ptr, grads), int(acc), ptr(ws2), stream_ptr())
+        return _gru_backward_done(ctx, dx, grads, acc)
+
+
+# What _GRULayerFn and _GRUTopLastFn share around their library calls.  params: the eight parameters of the layer,
+# (weight_ih, weight_ih_reverse, weight_hh, ..., bias_hh_reverse); grad_on: torch.is_grad_enabled() at the call
+# (inside forward it is always off, and needs_input_grad ignores it): an evaluation pass under no_grad must not
+# register copies or hold the reducer back.
+def _gru_operands(x, params, ws_floats):
+    """The forward's operands: dims, contiguous x, the direction pairs (w_ih, w_hh, b_ih, b_hh), y, the workspace and,
+    in 16-bit modes, the previous layer's own 16-bit copy of h as this layer's x16 (module note at _copies16)."""
+    B, T, IN = x.shape
+    H = params[2].shape[-1]
+    x = x.contiguous()
+    pairs = tuple(_dir_pair(params[2 * i], params[2 * i + 1]) for i in range(4))
+    _check_cuda(x, *pairs)
+    y = torch.empty((B, T, 2 * H), device=x.device, dtype=torch.float32)
+    ws = torch.empty(int(getattr(_lib.lib(), ws_floats)(B, T, IN, H, 0)), device=x.device)
+    x16 = _copy16_get(x) if IN % 8 == 0 else None
+    return (B, T, IN, H), x, pairs, y, ws, x16
+
+
+def _gru_forward_done(ctx, grad_on, dims, x, pairs, y, ws, x16, params):
+    ctx.x16 = x16
+    ctx.save_for_backward(x, pairs[0], pairs[1], y, ws)
+    ctx.dims = dims
+    ctx.params = params
+    ctx.prec = _lib.matmul_precision()   # the backward runs at its forward's precision
+    red = _reducer_of(params[0])
+    if red is not None and grad_on and any(ctx.needs_input_grad):
+        red.persistent_pending(1)      # collectives wait until this layer's recurrence is enqueued
+
+
+def _gru_backward_buffers(ctx, ws_floats):
+    """(saved tensors, dims, dx or None, (dw_ih, dw_hh, db_ih, db_hh), acc, the backward workspace).  acc: the four
+    gradients are the parameters' own stacked .grad (FlatParams), accumulated into in place."""
+    x, w_ih, w_hh, y, ws = ctx.saved_tensors
+    B, T, IN, H = ctx.dims
+    P = ctx.params
+    dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+    grads = [_grad_pair(P[2 * i], P[2 * i + 1]) for i in range(4)]
+    acc = all(t is not None for t in grads) and all(ctx.needs_input_grad[2:])
+    if not acc:
+        grads = [torch.empty_like(w_ih), torch.empty_like(w_hh), torch.empty((2, 3 * H), device=x.device),
+                 torch.empty((2, 3 * H), device=x.device)]
+    ws2 = torch.empty(int(getattr(_lib.lib(), ws_floats)(B, T, IN, H, 1)), device=x.device)
+    return (x, w_ih, w_hh, y, ws), ctx.dims, dx, grads, acc, ws2
+
+
+def _gru_backward_done(ctx, dx, grads, acc):
+    """The reducer hand-shake and backward's return tuple: None for gradients accumulated in place."""
+    red = _reducer_of(ctx.params[0])
+    if red is not None:
+        red.persistent_done()
         if acc:
-            return (dx, None) + (None,) * 8
-        return (dx, None, dw_ih[0], dw_ih[1], dw_hh[0], dw_hh[1], db_ih[0], db_ih[1], db_hh[0], db_hh[1])
+            red.mark_ready(ctx.params)
+    if acc:
+        return (dx, None) + (None,) * 8
+    return (dx, None) + tuple(g[d] for g in grads for d in (0, 1))
 
 
 class BiGRU(tnn.Module):
