@@ -612,6 +612,52 @@ int srk_dwconv2d_nhwc_bwd(const float* x, int64_t N, int64_t H, int64_t W, int64
 int srk_avgpool_nhwc_fwd(const float* x, int64_t N, int64_t HW, int64_t C, float* y, void* stream);
 int srk_avgpool_nhwc_bwd(const float* dy, int64_t N, int64_t HW, int64_t C, float* dx, void* stream);
 
+/* ---------------------------------------------------------------- SpecAugment on a feature map
+ * Time warp, frequency masks and time masks (Park et al., Interspeech 2019) on a batch of feature clips, the
+ * random draws made explicit and drawn on the device (features.spec_augment / specaug_draw; no reference
+ * counterpart).  All tensors fp32 and contiguous; a clip is [T][F] with time_major = 1 (what every plugin feeds its
+ * network) or [F][T] with time_major = 0 (the layout of K1 layout 0 and K3 transposed 0).
+ *
+ * params: int32 [B][P] on the device, P = 2 + 2 NF + 2 NT, 0 <= NF, NT <= 4; clip b holds
+ *   {c, w, f0_0, fw_0, .., f0_{NF-1}, fw_{NF-1}, t0_0, tw_0, .., t0_{NT-1}, tw_{NT-1}}.
+ *
+ * srk_specaug_apply computes per clip, in this order (y may be x: in place):
+ *  1. the fill value: fill_value (fill_mode 0), or the mean of the clip's T F input elements (fill_mode 1; fp32,
+ *     summed in a fixed order that does not depend on the layout, no floating-point atomics);
+ *  2. the time warp that moves frame c to frame w: output frame t reads source position s(t), an exact rational,
+ *       s = t c / w (t <= w),   s = c + (t - w)(T - 1 - c) / (T - 1 - w) (t > w);
+ *     with i = floor(s) and a = frac(s) = (float)(num % den) / (float)den: a == 0 copies x[i] bit for bit and reads
+ *     nothing else, otherwise x[i] + a (x[i+1] - x[i]) in fp32 (three roundings, no contraction).  c == w is the
+ *     identity: every frame a bit-exact copy;
+ *  3. the masks: an element whose feature index lies in any [f0_j, f0_j + fw_j) or whose frame lies in any
+ *     [t0_j, t0_j + tw_j) becomes the fill value.  Width 0 masks nothing; masks may overlap.
+ * Valid parameters: c == w with both in [0, T-1], or both c and w in [1, T-2]; f0, fw >= 0 and f0 + fw <= F;
+ * t0, tw >= 0 and t0 + tw <= T.  The parameters live on the device (no host check): the kernel validates a clip's
+ * row before it reads anything through it, and a clip with an invalid row gets NaN in its whole output (K2-VTLP's
+ * convention); the other clips are unaffected and no out-of-range address is formed.
+ * One launch, one workgroup per clip, the clip staged in LDS: one HBM read and one write per element, both along
+ * the contiguous axis in either layout, 16-byte accesses when T F % 4 == 0 and x, y are 16-byte aligned (a scalar
+ * path otherwise).  Domain: T F <= SRK_SPECAUG_MAX_ELEMS.
+ * Checked on the host before any device work, SRK_ERR_INVALID with "specaug" in srk_last_error(): T F above the
+ * constant, B < 1, T or F < 1, NF or NT outside 0..4, a fill_mode other than 0 or 1, a fill_value that is not
+ * finite, a null pointer.  Profiler category "specaug" (one record per launch, with its algorithmic bytes).
+ *
+ * srk_specaug_draw draws the parameters of B clips on the device (one launch, graph-replayable) from the state and
+ * hash of srk_uniform_f64_state: state = uint64[2] {base, counter}, seed = base + 0xD1B54A32D192ED03 * counter,
+ * z_i = the splitmix64 finaliser of seed + 0x9E3779B97F4A7C15 * (i + 1), r_i(n) = ((z_i >> 32) * n) >> 32, an exact
+ * integer in [0, n).  Clip b uses i = b P + k, k in this order:
+ *   k = 0: c = W + 1 + r(T - 2W - 2);   k = 1: w = c - W + r(2W + 1)   (W == 0: c = w = 0);
+ *   k = 2 + 2j: fw_j = r(f_max + 1);    k = 3 + 2j: f0_j = r(F - fw_j + 1);
+ *   k = 2 + 2NF + 2j: tw_j = r(t_max + 1);   k = 3 + 2NF + 2j: t0_j = r(T - tw_j + 1)
+ * (a width is drawn before its start and stored after it); then the call advances state[1] by one.  Every drawn row
+ * is valid for srk_specaug_apply.  The host refuses, as above: W < 0, W > 0 with T < 2W + 3, f_max outside [0, F],
+ * t_max outside [0, T], B, T or F < 1 (or T, F above 2^30), NF or NT outside 0..4, a null pointer.               */
+#define SRK_SPECAUG_MAX_ELEMS 15840   /* 98 x 120, 49 x 321, 51 x 39 and 98 x 40 fit; the staged clip is <= 62 KB */
+int srk_specaug_apply(const float* x, int64_t B, int64_t T, int64_t F, int time_major, const int32_t* params,
+                      int NF, int NT, int fill_mode, float fill_value, float* y, void* stream);
+int srk_specaug_draw(uint64_t* state, int64_t B, int64_t T, int64_t F, int W, int NF, int f_max, int NT, int t_max,
+                     int32_t* params_out, void* stream);
+
 /* ---------------------------------------------------------------- diagnostics (tests only)
  * Directed checks of two instruction patterns (csrc/diag.hip; tests/test_diag_gpu.py):
  * srk_diag_acc_store: the row-staged data gradient's epilogue (raw buffer stores of 32x32 MFMA

@@ -6,6 +6,7 @@ feature kernels K1-K3 also take int16 PCM (the WAV samples: half the bytes to up
 values).  A CPU tensor is copied to the current GPU first (the reference forward receives CPU
 batches, training.py:86).  There is no CPU path: without a GPU and libsrk.so these raise.
 """
+import collections
 import ctypes
 
 import torch
@@ -174,6 +175,147 @@ def vtlp_bins(alpha):
     bins = (ctypes.c_int32 * 122)()
     call("srk_vtlp_bins", float(alpha), bins)
     return list(bins)
+
+
+# ---------------------------------------------------------------- SpecAugment (srk_specaug_apply / _draw)
+SPECAUG_MAX_ELEMS = 15840     # SRK_SPECAUG_MAX_ELEMS (include/srk.h): the largest clip the kernel stages
+SPECAUG_MAX_MASKS = 4
+
+
+class SpecAugPolicy(collections.namedtuple("SpecAugPolicy", "W NF f_max NT t_max p fill")):
+    """A checked SpecAugment policy (``specaug_policy``).  W: the warped frame moves by at most W frames;
+    NF masks of up to f_max features; NT masks of up to min(t_max, floor(p T)) frames; fill: "mean" (each
+    clip's own mean) or "zero"."""
+    __slots__ = ()
+
+    @property
+    def n_params(self):
+        """P: the int32 words of one clip's parameter row {c, w, (f0, fw) x NF, (t0, tw) x NT}."""
+        return 2 + 2 * self.NF + 2 * self.NT
+
+    def t_max_for(self, T):
+        """The effective time-mask bound on clips of T frames: min(t_max, floor(p T))."""
+        return min(self.t_max, int(self.p * T))
+
+    def check_shape(self, T, F):
+        """Raise ValueError unless clips of T frames x F features are inside this policy's domain."""
+        if self.W > 0 and T < 2 * self.W + 3:
+            raise ValueError("specaug: W = %d needs T >= %d frames, got %d" % (self.W, 2 * self.W + 3, T))
+        if self.f_max > F:
+            raise ValueError("specaug: f_max = %d is above the %d features" % (self.f_max, F))
+        if self.t_max > T:
+            raise ValueError("specaug: t_max = %d is above the %d frames" % (self.t_max, T))
+        if T * F > SPECAUG_MAX_ELEMS:
+            raise ValueError("specaug: clips of %d x %d are above SPECAUG_MAX_ELEMS = %d" % (T, F, SPECAUG_MAX_ELEMS))
+        return self
+
+
+def specaug_policy(W, NF, f_max, NT, t_max, p=1.0, fill="mean"):
+    """Check and normalise a SpecAugment policy -> ``SpecAugPolicy`` (pure Python: no GPU needed).
+    W, f_max, t_max >= 0 and 0 <= NF, NT <= 4 are integers, 0 <= p <= 1, fill is "mean" or "zero".  What depends
+    on the clip shape (W against T, f_max against F, the effective t_max) is applied where T and F are known:
+    ``SpecAugPolicy.check_shape`` / ``t_max_for``."""
+    vals = []
+    for name, v in (("W", W), ("NF", NF), ("f_max", f_max), ("NT", NT), ("t_max", t_max)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError("specaug: %s must be an integer, got %r" % (name, v))
+        v = int(v)
+        if v < 0 or v >= 1 << 30:
+            raise ValueError("specaug: %s must be >= 0 (and below 2^30), got %d" % (name, v))
+        vals.append(v)
+    W, NF, f_max, NT, t_max = vals
+    if NF > SPECAUG_MAX_MASKS or NT > SPECAUG_MAX_MASKS:
+        raise ValueError("specaug: at most %d masks of each kind, got NF %d NT %d" % (SPECAUG_MAX_MASKS, NF, NT))
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError("specaug: p must be in [0, 1], got %r" % (p,))
+    if fill not in ("mean", "zero"):
+        raise ValueError("specaug: fill must be 'mean' or 'zero', got %r" % (fill,))
+    return SpecAugPolicy(W, NF, f_max, NT, t_max, p, fill)
+
+
+def as_specaug_policy(policy):
+    """A ``SpecAugPolicy`` from one, or from a sequence (W, NF, f_max, NT, t_max[, p[, fill]])."""
+    return policy if isinstance(policy, SpecAugPolicy) else specaug_policy(*policy)
+
+
+# SpecAugment draws: device index -> uint64[2] {base seed, call counter}, a state of its own exactly as
+# _VTLP_STATE is (another salt): turning SpecAugment on moves neither the dropout masks nor the VTLP factors.
+_SPECAUG_STATE = {}
+_SPECAUG_SALT = 0x5350454341554721   # "SPECAUG!"
+
+
+def _specaug_state(device):
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    st = _SPECAUG_STATE.get(idx)
+    if st is None:
+        seed = torch.cuda.default_generators[idx].initial_seed()
+        dist = torch.distributed
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        base = ((seed * 0x9E3779B97F4A7C15) ^ (rank * 0xC2B2AE3D27D4EB4F) ^ _SPECAUG_SALT) & _MASK63
+        st = torch.tensor([base, 0], dtype=torch.int64, device=torch.device("cuda", idx))
+        _SPECAUG_STATE[idx] = st
+    return st
+
+
+def specaug_reseed(seed, device=None):
+    """Reset the SpecAugment draw state of ``device`` (default: the current one): base = ``seed``, counter = 0."""
+    require_gpu()
+    idx = torch.cuda.current_device() if device is None else torch.device(device).index
+    idx = torch.cuda.current_device() if idx is None else idx
+    _SPECAUG_STATE[idx] = torch.tensor([int(seed) & _MASK63, 0], dtype=torch.int64, device=torch.device("cuda", idx))
+
+
+def specaug_state(device=None):
+    """(base, counter) of the SpecAugment draw state (synchronizes; for tests and logs)."""
+    require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    base, counter = _specaug_state(dev).tolist()
+    return base, counter
+
+
+def specaug_draw(B, T, F, policy, out=None):
+    """The SpecAugment parameters of B clips of T frames x F features: int32 [B, P] on the current device
+    (srk_specaug_draw; row layout: include/srk.h).  Draw k of a process hashes (base, k, clip, slot) on the device
+    and the kernel itself advances k, so an eager call and a replay of a captured one are the same arithmetic."""
+    require_gpu()
+    pol = as_specaug_policy(policy)
+    P = pol.n_params
+    dev = torch.device("cuda", torch.cuda.current_device()) if out is None else out.device
+    out = torch.empty((B, P), device=dev, dtype=torch.int32) if out is None else out
+    if out.dtype != torch.int32 or tuple(out.shape) != (B, P) or not out.is_contiguous() or out.device.type != "cuda":
+        raise SrkError("specaug_draw: out must be a contiguous int32 device tensor of shape (%d, %d)" % (B, P))
+    call("srk_specaug_draw", ptr(_specaug_state(dev)), B, T, F, pol.W, pol.NF, pol.f_max, pol.NT, pol.t_max_for(T),
+         ptr(out), stream_ptr())
+    return out
+
+
+def spec_augment(x, params, policy, time_major=True, out=None):
+    """SpecAugment (srk_specaug_apply) on a batch of feature clips: x float32 [B, T, F] (``time_major``, what the
+    plugins feed their networks) or [B, F, T] on the device; params int32 [B, P] (``specaug_draw``, or any
+    sequence of rows: uploaded).  Of ``policy`` only NF, NT and the fill are used here.  ``out=x`` works in place.
+    A clip whose row is invalid comes back all NaN (the values live on the device: no host check)."""
+    require_gpu()
+    pol = as_specaug_policy(policy)
+    if not torch.is_tensor(x) or x.dim() != 3 or x.dtype != torch.float32 or x.device.type != "cuda" \
+            or not x.is_contiguous():
+        raise SrkError("spec_augment: x must be a contiguous float32 device tensor [B, T, F] (or [B, F, T])")
+    B = x.shape[0]
+    T, F = (x.shape[1], x.shape[2]) if time_major else (x.shape[2], x.shape[1])
+    if not torch.is_tensor(params):
+        params = torch.as_tensor(params, dtype=torch.int32)
+    if params.dtype != torch.int32 or tuple(params.shape) != (B, pol.n_params):
+        raise SrkError("spec_augment: params must be int32 of shape (%d, %d), got %s %s"
+                       % (B, pol.n_params, params.dtype, tuple(params.shape)))
+    params = params.to(x.device).contiguous()
+    out = torch.empty_like(x) if out is None else out
+    if out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise SrkError("spec_augment: out must match x (shape, float32, contiguous, same device)")
+    if B == 0:
+        return out
+    call("srk_specaug_apply", ptr(x), B, T, F, 1 if time_major else 0, ptr(params), pol.NF, pol.NT,
+         1 if pol.fill == "mean" else 0, 0.0, ptr(out), stream_ptr())
+    return out
 
 
 def mfcc(pcm, time_major=False, out=None):

@@ -9,6 +9,43 @@ LABELS = ['yes', 'no', 'up', 'down', 'left', 'right', 'on', 'off', 'stop', 'go',
 DEVICE = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
 
 
+def check_specaug(specaug, T, F):
+    """The constructor argument ``specaug`` of a plugin whose network reads [T, F] clips, as a checked
+    ``features.SpecAugPolicy``, or None.  Accepts a policy or a sequence (W, NF, f_max, NT, t_max[, p[, fill]])."""
+    if specaug is None:
+        return None
+    from .. import features
+    return features.as_specaug_policy(specaug).check_shape(T, F)
+
+
+def apply_specaug(net, feat, specaug_params=None):
+    """SpecAugment for the plugins (``Network(specaug=...)``): masks and warps ``feat``, the time-major feature
+    tensor [B, T, F] the network is about to read, IN PLACE and returns it.  Training mode only — ``eval()`` and
+    ``specaug=None`` leave ``feat`` untouched, bit for bit.  The parameters are ``specaug_params`` (int32 [B, P],
+    for tests) or a fresh device draw into one persistent buffer per (device, batch size), kept for the module's
+    life as the VTLP factors are: a captured step of the full batch keeps its address while a short last batch
+    runs eagerly on another.  ``net.last_specaug`` holds the parameters of the last augmented batch."""
+    pol = net.specaug
+    if pol is None:
+        if specaug_params is not None:
+            raise ValueError("specaug_params needs a network built with specaug=... (NF, NT and the fill come from it)")
+        return feat
+    if not net.training:
+        return feat
+    from .. import features
+    B, T, F = feat.shape
+    if specaug_params is None:
+        key = (feat.device.index, B)
+        buf = net._specaug_bufs.get(key)
+        if buf is None:
+            buf = net._specaug_bufs[key] = torch.empty((B, pol.n_params), device=feat.device, dtype=torch.int32)
+        specaug_params = features.specaug_draw(B, T, F, pol, out=buf)
+    elif not torch.is_tensor(specaug_params):
+        specaug_params = torch.as_tensor(specaug_params, dtype=torch.int32).to(feat.device)
+    net.last_specaug = specaug_params
+    return features.spec_augment(feat, specaug_params, pol, time_major=True, out=feat)
+
+
 def accuracy(model, dataset, filename, batchsize=2):
     """Overall accuracy (%) on ``dataset``; appends it as one line to ``filename``."""
     total, correct = 0, 0

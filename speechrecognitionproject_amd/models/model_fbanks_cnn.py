@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from .. import features
 from ..nn import Conv2d, Dropout, Linear, MaxPool1d, MaxPool2d, conv1_pool, conv_pool
-from ._common import DEVICE, accuracy, class_accuracy   # noqa: F401
+from ._common import DEVICE, accuracy, apply_specaug, check_specaug, class_accuracy   # noqa: F401
 
 
 def filter_banks(sample):
@@ -36,13 +36,22 @@ class Network(nn.Module):
     ``None`` (the default, and the reference's constructor call) never warps.  ``eval()`` never warps
     either (dataset_top.py warps under ``self.train`` only).  The factors of the last drawn batch are in
     ``last_alpha`` (float64 [B], one persistent buffer per batch size: a captured step reads a static
-    address)."""
+    address).
 
-    def __init__(self, vtlp=None):
+    ``specaug=(W, NF, f_max, NT, t_max)`` (or a ``features.SpecAugPolicy``) turns on SpecAugment for training-mode
+    forwards: a time warp, NF frequency masks and NT time masks on the feature map the network reads, drawn on
+    the device (features.spec_augment); ``None`` (the default) and ``eval()`` leave the features untouched.  The
+    parameters of the last augmented batch are in ``last_specaug`` (int32 [B, P]).  With VTLP on as well, the
+    bank is warped first and the warped features are masked."""
+
+    def __init__(self, vtlp=None, specaug=None):
         super().__init__()
         self.vtlp = check_vtlp(vtlp)
         self.last_alpha = None
         self._alpha_bufs = {}
+        self.specaug = check_specaug(specaug, 98, 120)
+        self.last_specaug = None
+        self._specaug_bufs = {}
         self.conv1 = Conv2d(1, 64, kernel_size=(7, 3), padding=(3, 1))
         self.maxpool1 = MaxPool2d((1, 3))
         self.conv2 = Conv2d(64, 128, (1, 7), padding=(0, 3))
@@ -64,11 +73,12 @@ class Network(nn.Module):
         self.last_alpha = features.vtlp_draw(n, self.vtlp[0], self.vtlp[1], out=buf)
         return buf
 
-    def forward(self, x, alpha=None):
+    def forward(self, x, alpha=None, specaug_params=None):
         with torch.no_grad():
             if alpha is None and self.training and self.vtlp is not None:
                 alpha = self._draw_alpha(x.shape[0] if len(x.shape) > 1 else 1)
             inx = features.fbank(x, alpha=alpha)          # [B, 98, 120]
+            inx = apply_specaug(self, inx, specaug_params)
         # fused conv1 + maxpool1: NHWC [B, 98, 40, 64] (its fp32 copy skipped when conv2 reads the 16-bit one)
         h = conv1_pool(inx, self.conv1, self.maxpool1, next_conv_pool16=True)
         h = conv_pool(h, self.conv2, self.maxpool2)      # fused conv2 + maxpool2: [B, 98, 10, 128]

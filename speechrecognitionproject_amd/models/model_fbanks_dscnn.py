@@ -26,7 +26,7 @@ import torch.nn as nn
 from .. import features
 from ..nn import BatchNorm1d, Conv2d, DepthwiseConv2d, GlobalAvgPool2d, Linear, MaxPool2d, _copy16_drop, conv1_pool
 from . import model_fbanks_cnn
-from ._common import DEVICE, accuracy, class_accuracy   # noqa: F401  (plugin API)
+from ._common import DEVICE, accuracy, apply_specaug, check_specaug, class_accuracy   # noqa: F401  (plugin API)
 from .model_fbanks_cnn import filter_banks              # noqa: F401  (plugin API)
 
 
@@ -47,15 +47,19 @@ class DSBlock(nn.Module):
 
 class Network(nn.Module):
     """``vtlp`` as in model_fbanks_cnn.Network (whose draw it shares): ``None`` never warps, ``(lo, hi)`` warps
-    training-mode forwards; the factors of the last drawn batch are in ``last_alpha``."""
+    training-mode forwards; the factors of the last drawn batch are in ``last_alpha``.  ``specaug`` likewise as in
+    model_fbanks_cnn.Network: SpecAugment on the (warped) filter banks, its parameters in ``last_specaug``."""
 
     _draw_alpha = model_fbanks_cnn.Network._draw_alpha
 
-    def __init__(self, vtlp=None):
+    def __init__(self, vtlp=None, specaug=None):
         super().__init__()
         self.vtlp = model_fbanks_cnn.check_vtlp(vtlp)
         self.last_alpha = None
         self._alpha_bufs = {}
+        self.specaug = check_specaug(specaug, 98, 120)
+        self.last_specaug = None
+        self._specaug_bufs = {}
         self.conv1 = Conv2d(1, 64, kernel_size=(7, 3), padding=(3, 1))
         self.maxpool1 = MaxPool2d((1, 3))
         self.bn1 = BatchNorm1d(64)
@@ -66,11 +70,12 @@ class Network(nn.Module):
         self.pool = GlobalAvgPool2d()
         self.fc = Linear(256, 12)
 
-    def forward(self, x, alpha=None):
+    def forward(self, x, alpha=None, specaug_params=None):
         with torch.no_grad():
             if alpha is None and self.training and self.vtlp is not None:
                 alpha = self._draw_alpha(x.shape[0] if len(x.shape) > 1 else 1)
             inx = features.fbank(x, alpha=alpha)              # [B, 98, 120]
+            inx = apply_specaug(self, inx, specaug_params)
         h = conv1_pool(inx, self.conv1, self.maxpool1)        # fused conv1 + maxpool1: NHWC [B, 98, 40, 64]
         # 16-bit training steps: the fused kernel hands its output's 16-bit copy over for a dense conv2, which this
         # model does not have.  bn1 reads the fp32 tensor, so nobody would take the entry, and it would keep h — and

@@ -6,7 +6,7 @@ import torch.nn as nn
 
 from .. import features
 from ..nn import BiGRU, Linear
-from ._common import DEVICE, accuracy, class_accuracy   # noqa: F401
+from ._common import DEVICE, accuracy, apply_specaug, check_specaug, class_accuracy   # noqa: F401
 
 
 def compute_spec(sample):
@@ -15,12 +15,21 @@ def compute_spec(sample):
 
 
 class Network(nn.Module):
-    def __init__(self, num_features=512, num_layers=2):
+    """``specaug=(W, NF, f_max, NT, t_max)`` (or a ``features.SpecAugPolicy``) turns on SpecAugment for training-mode
+    forwards: a time warp, NF frequency masks and NT time masks on the [49, 321] spectrogram the GRU reads, drawn
+    on the device (features.spec_augment); ``None`` (the default) and ``eval()`` leave the features untouched.  The
+    parameters of the last augmented batch are in ``last_specaug`` (int32 [B, P])."""
+
+    def __init__(self, num_features=512, num_layers=2, specaug=None):
         super().__init__()
+        self.specaug = check_specaug(specaug, 49, 321)
+        self.last_specaug = None
+        self._specaug_bufs = {}
         self.gru = BiGRU(321, num_features, num_layers=num_layers, bidirectional=True, batch_first=True)
         self.fc = Linear(num_features * 2, 12)
 
-    def forward(self, x):
+    def forward(self, x, specaug_params=None):
         with torch.no_grad():
             inx = features.spec(x, transposed=True)     # [B, 49, 321] = transpose(spec, 1, 2)
+            inx = apply_specaug(self, inx, specaug_params)
         return self.fc(self.gru.forward_last(inx))

@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from .. import features
 from ..nn import Conv2d, Dropout, Linear, MaxPool1d, MaxPool2d, conv1_pool
-from ._common import DEVICE, accuracy, class_accuracy   # noqa: F401
+from ._common import DEVICE, accuracy, apply_specaug, check_specaug, class_accuracy   # noqa: F401
 
 
 def compute_spec(sample):
@@ -23,8 +23,14 @@ def compute_spec(sample):
 
 
 class Network(nn.Module):
-    def __init__(self):
+    """``specaug`` as in model_spec_bgru.Network: SpecAugment on the [49, 321] spectrogram of training-mode
+    forwards, its parameters in ``last_specaug``; ``None`` (the default) and ``eval()`` leave it untouched."""
+
+    def __init__(self, specaug=None):
         super().__init__()
+        self.specaug = check_specaug(specaug, 49, 321)
+        self.last_specaug = None
+        self._specaug_bufs = {}
         self.bn1 = nn.BatchNorm2d(1)
         self.conv1 = Conv2d(1, 64, (3, 7), padding=(1, 3))
         self.maxpool1 = MaxPool2d((1, 5))
@@ -37,9 +43,10 @@ class Network(nn.Module):
         self.fc1 = Linear(512, 256)
         self.fc2 = Linear(256, 12)
 
-    def forward(self, x):
+    def forward(self, x, specaug_params=None):
         with torch.no_grad():
             inx = features.spec(x, transposed=True)        # [B, 49, 321]
+            inx = apply_specaug(self, inx, specaug_params)
         h = conv1_pool(inx, self.conv1, self.maxpool1)   # fused conv1 + maxpool1: NHWC [B, 49, 64, 64]
         h = self.maxpool2(self.conv2(h))                  # [B, 49, 12, 128]
         h = self.conv4(self.conv3(h))                     # [B, 49, 1, 512]

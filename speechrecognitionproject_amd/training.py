@@ -28,6 +28,12 @@ default, or a fixed number) and skips any step whose gradients overflowed (optim
 factor drawn on the device (legacy/model_8/dataset_top.py:245-267); the draw's counter lives on the
 device too, so replayed and eager steps draw the same sequence.  ``--model fbanks_dscnn`` is the small-footprint
 depthwise-separable CNN on the same filter banks (models/model_fbanks_dscnn.py).
+``--specaug W,NF,FMAX,NT,TMAX`` (the MFCC, filter-bank and spectrogram plugins of SPECAUG_SHAPES, off by default) runs
+SpecAugment on the feature map each training step reads: one frame moved by up to W frames with the rest stretched
+linearly around it, NF masks of up to FMAX features and NT masks of up to TMAX frames, filled with the clip's mean
+(``--specaug-fill zero``: with 0).  One draw launch and one in-place launch per step (srk_specaug_draw / _apply);
+the draw's state is its own device counter, so the flag moves neither the dropout masks nor the VTLP factors, and a
+replayed step draws what the eager step would have drawn.  Evaluation never augments.
 """
 import argparse
 import importlib
@@ -45,6 +51,9 @@ from .optim import Adam, FlatParams, LossScaler
 
 PLUGINS = ("mfcc_bgru", "fbanks_cnn", "spec_bgru", "resnet_bgru", "mfrn_bgru", "cnn_bgru", "spec_cnn", "resnet_dconv",
            "mfcc_bgru_att", "fbanks_cnn_pcen", "fbanks_dscnn")
+# the plugins whose Network takes specaug=..., with the (frames, features) of the clips their networks read
+SPECAUG_SHAPES = {"mfcc_bgru": (51, 39), "mfcc_bgru_att": (51, 39), "fbanks_cnn": (98, 120), "fbanks_cnn_pcen": (98, 120),
+                  "fbanks_dscnn": (98, 120), "spec_bgru": (49, 321), "spec_cnn": (49, 321)}
 
 
 def parse(argv=None):
@@ -93,7 +102,25 @@ def parse(argv=None):
                    help="fbanks_cnn, fbanks_cnn_pcen, fbanks_dscnn: warp each training clip's mel filter bank by a factor drawn uniformly from "
                         "[LO, HI) (vocal-tract-length perturbation, the reference's legacy/model_8 trains with "
                         "0.9,1.1); off by default")
+    p.add_argument('--specaug', default=None, metavar='W,NF,FMAX,NT,TMAX',
+                   help="SpecAugment on each training clip's feature map (%s): one frame moved by up to W frames, "
+                        "NF masks of up to FMAX features and NT masks of up to TMAX frames, all drawn on the device; "
+                        "e.g. 5,2,15,2,12 for the 98 x 120 filter banks; off by default" % ', '.join(SPECAUG_SHAPES))
+    p.add_argument('--specaug-fill', choices=('mean', 'zero'), default='mean',
+                   help="--specaug: what a masked element becomes: its clip's mean (default) or 0")
     args = p.parse_args(argv)
+    if args.specaug is not None:
+        if args.model not in SPECAUG_SHAPES:
+            p.error('--specaug applies to --model %s only' % ', '.join(SPECAUG_SHAPES))
+        try:
+            vals = [int(v) for v in args.specaug.split(',')]
+            if len(vals) != 5:
+                raise ValueError('five integers, got %d' % len(vals))
+            from .features import specaug_policy
+            args.specaug = specaug_policy(*vals, fill=args.specaug_fill).check_shape(*SPECAUG_SHAPES[args.model])
+        except ValueError as e:
+            p.error('--specaug takes W,NF,FMAX,NT,TMAX inside the domain of %s (%d frames x %d features): %s'
+                    % ((args.model,) + SPECAUG_SHAPES[args.model] + (e,)))
     if args.vtlp is not None:
         if args.model not in ('fbanks_cnn', 'fbanks_cnn_pcen', 'fbanks_dscnn'):
             p.error('--vtlp applies to --model fbanks_cnn, fbanks_cnn_pcen and fbanks_dscnn only')
@@ -145,6 +172,8 @@ def _train(args):
     net_args = {} if args.mode is None else {'mode': args.mode}
     if args.vtlp is not None:
         net_args['vtlp'] = args.vtlp
+    if args.specaug is not None:
+        net_args['specaug'] = args.specaug
     model = mod.Network(**net_args).to(device)
     if args.sync_bn:
         from .nn import convert_sync_batchnorm
