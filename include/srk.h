@@ -239,6 +239,17 @@ int srk_gemm_16_batched(int trans_a, int trans_b, int64_t M, int64_t N, int64_t 
                         int64_t sB, float beta, float* C, int64_t ldc, int64_t sC, int batch, void* stream);
 /* out[n] = beta * out[n] + sum_m X[m, n]  (bias gradients).                                 */
 int srk_colsum_f32(const float* X, int64_t M, int64_t N, int64_t ldx, float* out, float beta, void* stream);
+/* Debug: the launch plan of the GEMM these arguments describe, as text; no GPU needed.  operands16 = the
+ * 16-bit-operand entry points, has_rowsum = fused row sums, prec = -1 (the matmul_precision option) or 0 / 1 / 2,
+ * no_split / plan_batch = the internal fields of the same names (0 from the public entry points).  The four
+ * addresses are inspected for alignment and nullness only.  buf receives two lines,
+ *   "<profiler name>|<kernel and shape as srk_prof_kernels reports them>"
+ *   "reduce=<none|splitk_reduce|splitk_reduce4>[+rowsum] scratch=<floats of library scratch>";
+ * returns the status the GEMM itself would return for these arguments.                            */
+int srk_gemm_plan_describe(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
+                           int64_t ldc, int batch, int64_t sA, int64_t sB, int64_t sC, int bias_mode, int has_rowsum,
+                           int operands16, int prec, int no_split, int plan_batch, uint64_t a_addr, uint64_t b_addr,
+                           uint64_t c_addr, uint64_t bias_addr, char* buf, int64_t cap);
 
 /* ---------------------------------------------------------------- K5: bidirectional GRU layer
  * nn.GRU(in, H, bidirectional=True, batch_first=True), one layer, PyTorch gate order [r; z; n],

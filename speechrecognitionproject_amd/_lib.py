@@ -62,6 +62,9 @@ _SIGS = {
     "srk_gemm_16": [_I, _I, _I64, _I64, _I64, _F, _P, _I64, _P, _I64, _F, _P, _I64, _P, _I, _P],
     "srk_gemm_16_batched": [_I, _I, _I64, _I64, _I64, _F, _P, _I64, _I64, _P, _I64, _I64, _F, _P, _I64, _I64, _I, _P],
     "srk_colsum_f32": [_P, _I64, _I64, _I64, _P, _F, _P],
+    "srk_gemm_plan_describe": [_I, _I, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I64, _I64, _I64, _I, _I, _I, _I, _I, _I,
+                               ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p,
+                               _I64],
     "srk_gru_workspace_floats": [_I64, _I64, _I64, _I64, _I],
     "srk_gru_layer_fwd": [_P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P],
     "srk_gru_layer_bwd": [_P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],

@@ -11,7 +11,6 @@
 // Backward (training statistics):
 //   g = dy * act'(y);  dbeta = sum g;  dgamma = sum g * xhat
 //   dx = gamma * invstd / M * (M g - dbeta - xhat * dgamma);  dresidual = g
-#include <mutex>
 
 #include "srk_internal.h"
 
@@ -460,30 +459,7 @@ __global__ void bn_combine_kernel(const float* __restrict__ all, int world, int 
   }
 }
 
-struct BnScratch {
-  float* p = nullptr;
-  size_t floats = 0;
-};
-BnScratch g_bs[64];
-std::mutex g_bs_mu;
-
-int bn_scratch(size_t floats, float** out) {
-  int dev = 0;
-  SRK_CHECK_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_bs_mu);
-  BnScratch& s = g_bs[dev & 63];
-  if (s.floats < floats) {
-    if (s.p) {
-      SRK_CHECK_HIP(hipDeviceSynchronize());
-      SRK_CHECK_HIP(hipFree(s.p));
-    }
-    s.floats = floats + floats / 4;
-    SRK_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&s.p), s.floats * sizeof(float)));
-    g_scratch_gen.fetch_add(1);
-  }
-  *out = s.p;
-  return SRK_OK;
-}
+ScratchPool g_bs;   // per-chunk statistics / reduction partials
 
 // the element kernels by index width (32-bit channel arithmetic below 2^32 elements) and 16-bit copy
 template <int LP>
@@ -565,7 +541,7 @@ int srk_batchnorm_fwd16_mask(const float* x, int64_t M, int64_t C, const float* 
   const srk::BnGeom g = srk::bn_geom(M, (int)C);
   if (training) {
     float* part = nullptr;
-    if (int rc = srk::bn_scratch((size_t)2 * g.chunks * C, &part)) return rc;
+    if (int rc = srk::g_bs.get((size_t)2 * g.chunks * C, &part)) return rc;
     hipLaunchKernelGGL(srk::bn_stats_kernel, dim3((unsigned)((g.C4 + g.CQ - 1) / g.CQ), (unsigned)g.chunks), dim3(256),
                        0, s, x, g, part, part + (size_t)g.chunks * C);
     // one wave per channel (tree) or one lane per channel in 64-lane blocks (in order: C / 64 waves over the chip)
@@ -631,7 +607,7 @@ int srk_batchnorm_bwd16_mask(const float* x, const float* y, const uint8_t* relu
   srk::ProfScope prof("batchnorm_bwd", s, ((mk ? 12.5 : 16.0) + (lp ? 2.0 : 0.0)) * (double)M * C);
   const srk::BnGeom g = srk::bn_geom(M, (int)C);
   float* part = nullptr;
-  if (int rc = srk::bn_scratch((size_t)2 * g.chunks * C, &part)) return rc;
+  if (int rc = srk::g_bs.get((size_t)2 * g.chunks * C, &part)) return rc;
   hipLaunchKernelGGL(srk::bn_bwd_partial_kernel, dim3((unsigned)((g.C4 + g.CQ - 1) / g.CQ), (unsigned)g.chunks),
                      dim3(256), 0, s, x, y, mk, dy, g, save_mean, save_invstd, relu, part, part + (size_t)g.chunks * C);
   hipLaunchKernelGGL(srk::bn_dgamma_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, part,
@@ -654,7 +630,7 @@ int srk_batchnorm_stats(const float* x, int64_t M, int64_t C, float* stats, void
   srk::ProfScope prof("batchnorm_fwd", s, 4.0 * (double)M * C);
   const srk::BnGeom g = srk::bn_geom(M, (int)C);
   float* part = nullptr;
-  if (int rc = srk::bn_scratch((size_t)2 * g.chunks * C, &part)) return rc;
+  if (int rc = srk::g_bs.get((size_t)2 * g.chunks * C, &part)) return rc;
   hipLaunchKernelGGL(srk::bn_stats_kernel, dim3((unsigned)((g.C4 + g.CQ - 1) / g.CQ), (unsigned)g.chunks), dim3(256), 0,
                      s, x, g, part, part + (size_t)g.chunks * C);
   hipLaunchKernelGGL(srk::bn_local_stats_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, s, part,
@@ -702,7 +678,7 @@ int srk_batchnorm_bwd_reduce(const float* x, const float* y, const float* dy, in
   srk::ProfScope prof("batchnorm_bwd", s, 12.0 * (double)M * C);
   const srk::BnGeom g = srk::bn_geom(M, (int)C);
   float* part = nullptr;
-  if (int rc = srk::bn_scratch((size_t)2 * g.chunks * C, &part)) return rc;
+  if (int rc = srk::g_bs.get((size_t)2 * g.chunks * C, &part)) return rc;
   hipLaunchKernelGGL(srk::bn_bwd_partial_kernel, dim3((unsigned)((g.C4 + g.CQ - 1) / g.CQ), (unsigned)g.chunks),
                      dim3(256), 0, s, x, y, nullptr, dy, g, save_mean, save_invstd, relu, part,
                      part + (size_t)g.chunks * C);
@@ -731,17 +707,3 @@ int srk_batchnorm_bwd_dx(const float* x, const float* y, const float* dy, int64_
 }
 
 }  // extern "C"
-
-namespace srk {
-int release_bn_scratch() {
-  std::lock_guard<std::mutex> lk(g_bs_mu);
-  SRK_CHECK_HIP(hipDeviceSynchronize());
-  for (BnScratch& s : g_bs) {
-    if (s.p) SRK_CHECK_HIP(hipFree(s.p));
-    s.p = nullptr;
-    s.floats = 0;
-  }
-  g_scratch_gen.fetch_add(1);
-  return SRK_OK;
-}
-}  // namespace srk

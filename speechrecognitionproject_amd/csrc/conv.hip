@@ -10,7 +10,6 @@
 //   wgrad    : dWt[(kh,kw,ci), co] = sum_p X[n, ho*s+kh-ph, wo*s+kw-pw, ci] dY[p, co]   (K = N*Ho*Wo)
 // The gathers are done by the operand loaders (no im2col buffer).  Weights are re-laid out once
 // per call from the torch layout [Co][Ci][KH][KW] (a 1.4 MB copy for the whole fbanks_cnn model).
-#include <mutex>
 #include <type_traits>
 
 #include "gemm.h"
@@ -965,34 +964,11 @@ __global__ __launch_bounds__(64 * kCsWaves) void colsum_blocks_kernel(const floa
   }
 }
 
-struct ConvScratch {
-  float* p = nullptr;
-  size_t floats = 0;
-};
-ConvScratch g_cs[64];     // split-K slabs
-ConvScratch g_cs16[64];   // 16-bit operand sources
-ConvScratch g_csb[64];    // wgrad bias column-sum partials
-ConvScratch g_csd[64];    // dense activation / gradient of the pooled conv (split-K forward, backward dY)
-ConvScratch g_csy[64];    // conv_bwd: dY's 16-bit copy made with the bias sums (dY itself may sit in g_csd)
-std::mutex g_cs_mu;
-
-int conv_scratch(size_t floats, float** out, ConvScratch* pool = g_cs) {
-  int dev = 0;
-  SRK_CHECK_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_cs_mu);
-  ConvScratch& s = pool[dev & 63];
-  if (s.floats < floats) {
-    if (s.p) {
-      SRK_CHECK_HIP(hipDeviceSynchronize());
-      SRK_CHECK_HIP(hipFree(s.p));
-    }
-    s.floats = floats + floats / 4;
-    SRK_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&s.p), s.floats * sizeof(float)));
-    g_scratch_gen.fetch_add(1);
-  }
-  *out = s.p;
-  return SRK_OK;
-}
+ScratchPool g_cs;     // split-K slabs
+ScratchPool g_cs16;   // 16-bit operand sources
+ScratchPool g_csb;    // wgrad bias column-sum partials
+ScratchPool g_csd;    // dense activation / gradient of the pooled conv (split-K forward, backward dY)
+ScratchPool g_csy;    // conv_bwd: dY's 16-bit copy made with the bias sums (dY itself may sit in g_csd)
 
 // 16-bit sources (ConvArgs::a16 / b16) for matmul_precision bf16 / fp16 when every channel count is
 // a multiple of 8 and the fp32 tensors are 16-B aligned (option "conv16_sources", default on).
@@ -1017,7 +993,7 @@ int to16_all(int prec, const float* const* src, const int64_t* n, int cnt, unsig
   }
   float* base = nullptr;
   if (total) {
-    if (int rc = conv_scratch((total + 1) / 2, &base, g_cs16)) return rc;
+    if (int rc = g_cs16.get((total + 1) / 2, &base)) return rc;
   }
   ProfScope prof("conv_to16", s, bytes);
   for (int i = 0; i < cnt; ++i) {
@@ -1045,7 +1021,7 @@ int colsum8(int kind, int prec, const float* x, const uint8_t* arg, int64_t rows
   per = (per + RL - 1) / RL * RL;
   nblk = (rows + per - 1) / per;
   float* part = nullptr;
-  if (int rc = conv_scratch((size_t)nblk * C, &part, g_csb)) return rc;
+  if (int rc = g_csb.get((size_t)nblk * C, &part)) return rc;
   const double bytes = (double)rows * C * (4.0 + (kind == 1 ? 2.0 : kind == 2 ? 1.0 + 2.0 * kw : 0.0));
   ProfScope prof(kind == 0 ? "conv_colsum" : kind == 1 ? "conv_to16_colsum" : "conv_unpool16_colsum", s, bytes);
   const dim3 grid((unsigned)nblk), block(256);
@@ -2721,11 +2697,11 @@ template <int MODE>
 int split_scratch(ConvArgs& c, int splits) {
   c.partial = nullptr;
   if (splits > 1) {
-    if (int rc = conv_scratch((size_t)splits * c.M * c.Nn, &c.partial)) return rc;
+    if (int rc = g_cs.get((size_t)splits * c.M * c.Nn, &c.partial)) return rc;
   }
   c.colsum_part = nullptr;
   if (MODE == kWgrad && c.db && !c.a16) {
-    if (int rc = conv_scratch((size_t)splits * c.Nn, &c.colsum_part, g_csb)) return rc;
+    if (int rc = g_csb.get((size_t)splits * c.Nn, &c.colsum_part)) return rc;
   }
   return SRK_OK;
 }
@@ -2749,7 +2725,7 @@ int conv_gemm_finish(const ConvArgs& c, const ConvArgs& k, int splits, hipStream
     const bool pool = MODE == kFwd && c.pool_w;
     float* dense = c.out;
     if (pool) {
-      if (int rc = conv_scratch((size_t)c.M * c.Nn, &dense, g_csd)) return rc;
+      if (int rc = g_csd.get((size_t)c.M * c.Nn, &dense)) return rc;
     }
     launch_splitk_sum(k.partial, splits, c.M * c.Nn, c.Nn, MODE == kFwd ? c.bias : nullptr, dense, s);
     if (pool) {
@@ -2979,9 +2955,9 @@ int row_wgrad(const RowGrid& g, float* ws, float* dw, float* db, int dw_accumula
   const int64_t nslab = Conv2::KW * Conv2::Ci * Conv2::Co;
   float* slab = nullptr;
   float* bpart = nullptr;
-  if (int rc = conv_scratch((size_t)(g.G * nslab), &slab)) return rc;
+  if (int rc = g_cs.get((size_t)(g.G * nslab), &slab)) return rc;
   if (db)
-    if (int rc = conv_scratch((size_t)(g.G * Conv2::Co), &bpart, g_csb)) return rc;
+    if (int rc = g_csb.get((size_t)(g.G * Conv2::Co), &bpart)) return rc;
   launch(slab, bpart);
   launch_splitk_sum(slab, (int)g.G, nslab, Conv2::Co, nullptr, ws, s);
   if (db)
@@ -3180,7 +3156,7 @@ int conv_bwd(const float* x, int64_t N, int64_t H, int64_t W, int64_t Ci, const 
     d16[1] = const_cast<unsigned short*>(dy16);
     if (cs && !dy16) {
       float* d = nullptr;
-      if ((rc = srk::conv_scratch((size_t)(n[1] + 1) / 2, &d, srk::g_csy))) return rc;
+      if ((rc = srk::g_csy.get((size_t)(n[1] + 1) / 2, &d))) return rc;
       d16[1] = reinterpret_cast<unsigned short*>(d);
     }
     if ((rc = srk::to16_all(prec, src, n, dgrad_implicit ? 3 : 2, d16, s, ready))) return rc;
@@ -3423,7 +3399,7 @@ int srk_conv2d_nhwc_bwd_pool(const float* x, int64_t N, int64_t H, int64_t W, in
     // 16-bit-source modes: the dense dY straight as its 16-bit copy, the bias gradient from the pooled
     // gradient (each pooled value sits once in the dense dY, the rest are zeros), then the backward
     float* d = nullptr;
-    if (int rc = srk::conv_scratch((size_t)(N * Ho * Wo * Co + 1) / 2, &d, srk::g_csd)) return rc;
+    if (int rc = srk::g_csd.get((size_t)(N * Ho * Wo * Co + 1) / 2, &d)) return rc;
     unsigned short* dy16 = reinterpret_cast<unsigned short*>(d);
     if (db && srk::colsum8_ok(Co)) {   // the dense 16-bit dY and the bias gradient in one pass over the pooled dY
       if (int rc = srk::colsum8(2, prec, dy_pooled, argmax, rows, (int)Co, (int)pool_w, dy16, db, s)) return rc;
@@ -3442,7 +3418,7 @@ int srk_conv2d_nhwc_bwd_pool(const float* x, int64_t N, int64_t H, int64_t W, in
                          dy16);
   }
   float* dy = nullptr;   // else: the dense gradient in library scratch, then the plain backward
-  if (int rc = srk::conv_scratch((size_t)(N * Ho * Wo * Co), &dy, srk::g_csd)) return rc;
+  if (int rc = srk::g_csd.get((size_t)(N * Ho * Wo * Co), &dy)) return rc;
   hipLaunchKernelGGL(srk::unpool_kernel, dim3((unsigned)((rows * (Co / 4) + 255) / 256)), dim3(256), 0, s, dy_pooled,
                      argmax, rows, (int)Co, (int)pool_w, dy);
   SRK_CHECK_HIP(hipGetLastError());
@@ -3488,18 +3464,3 @@ int srk_maxpool_nhwc_bwd(const float* x, const float* dy, int64_t N, int64_t H, 
 }
 
 }  // extern "C"
-
-namespace srk {
-int release_conv_scratch() {
-  std::lock_guard<std::mutex> lk(g_cs_mu);
-  SRK_CHECK_HIP(hipDeviceSynchronize());
-  for (ConvScratch* pool : {g_cs, g_cs16, g_csb, g_csd, g_csy})
-    for (int d = 0; d < 64; ++d) {
-      if (pool[d].p) SRK_CHECK_HIP(hipFree(pool[d].p));
-      pool[d].p = nullptr;
-      pool[d].floats = 0;
-    }
-  g_scratch_gen.fetch_add(1);
-  return SRK_OK;
-}
-}  // namespace srk

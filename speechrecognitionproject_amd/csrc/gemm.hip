@@ -14,7 +14,6 @@
 // dW = dY^T X GEMM, fused: no separate pass over dY).
 #include <algorithm>
 #include <cstdlib>
-#include <mutex>
 #include <type_traits>
 
 #include "gemm.h"
@@ -1300,41 +1299,6 @@ inline double gemm_bytes(const GemmDesc& d, int esz) {
   return ((double)d.M * (double)d.K * esz + (double)d.K * (double)d.N * esz + c) * (double)d.batch;
 }
 
-template <int RND>
-int launch_skinny_rnd(const GemmDesc& d, int kind, hipStream_t s) {
-  ProfScope prof(RND == 0 ? "gemm_f32" : RND == 1 ? "gemm_bf16" : "gemm_f16", s,
-                 2.0 * (double)d.M * (double)d.N * (double)d.K);
-  prof.bytes(gemm_bytes(d, 4));
-  const char* kn = kind == 0 ? "skinny_n" : kind == 1 ? "skinny_m" : "skinny_k";
-  prof.detail("%s_kernel<%c%c> %lldx%lldx%lld", kn, d.ta ? 'T' : 'N', d.tb ? 'T' : 'N', (long long)d.M,
-              (long long)d.N, (long long)d.K);
-  if (kind == 0) {
-    const dim3 grid((unsigned)d.M);
-    if (d.tb) hipLaunchKernelGGL((skinny_n_kernel<RND, true>), grid, dim3(256), 0, s, d);
-    else hipLaunchKernelGGL((skinny_n_kernel<RND, false>), grid, dim3(256), 0, s, d);
-  } else if (kind == 1) {
-    const dim3 grid((unsigned)((d.N + 63) / 64));
-    if (d.ta) hipLaunchKernelGGL((skinny_m_kernel<RND, true>), grid, dim3(1024), 0, s, d);
-    else hipLaunchKernelGGL((skinny_m_kernel<RND, false>), grid, dim3(1024), 0, s, d);
-  } else {
-    const dim3 grid((unsigned)((d.N + 255) / 256), (unsigned)d.M);
-    if (d.ta) hipLaunchKernelGGL((skinny_k_kernel<RND, true>), grid, dim3(256), 0, s, d);
-    else hipLaunchKernelGGL((skinny_k_kernel<RND, false>), grid, dim3(256), 0, s, d);
-  }
-  SRK_CHECK_HIP(hipGetLastError());
-  return SRK_OK;
-}
-
-// Which skinny kernel takes this GEMM (-1: none; the matrix-core tiles run it).  Sizes keep each
-// kernel's per-thread loop short and its streamed operand a few MB at most.
-int skinny_kind(const GemmDesc& d) {
-  if (!g_opt_gemm_skinny || d.batch != 1 || d.plan_batch > 1 || d.A16 || d.B16 || d.K <= 0) return -1;
-  if (d.N <= 16 && !d.ta && d.M <= 65535 * 16 && d.M * d.K <= (int64_t)1 << 24) return 0;
-  if (d.M <= 16 && !d.tb && d.K <= 1024 && d.N * d.K <= (int64_t)1 << 24) return 1;
-  if (d.K <= 16 && !d.tb && d.M <= 65535 && d.M * d.N <= (int64_t)1 << 24) return 2;
-  return -1;
-}
-
 // ------------------------------------------------------------------ fp32: LDS-DMA ping-pong
 // gemm_p32_kernel: the exact-fp32 GEMM (v_mfma_f32_32x32x2_f32) on the structure of gemm_g16_kernel —
 // 256 x 256 tiles, two 4-wave groups running one section apart behind raw barriers, a ring of four
@@ -1702,341 +1666,257 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ X
   }
 }
 
-// ------------------------------------------------------------------ scratch (split-K slabs)
-struct Scratch {
-  float* p = nullptr;
-  size_t floats = 0;
+// ------------------------------------------------------------------ host path: gemm_plan decides, gemm_launch runs
+ScratchPool g_scratch;   // split-K slabs and row-sum partials, the stream-K slab, colsum_f32's partials
+
+// Measurement knobs of the environment (tools/gemm_bench.py, A/B scripts); gemm_plan reads them once.
+struct GemmEnv {
+  int remap;     // SRK_GEMM_REMAP (default 1): the XCD-aware block remap, 0 = off
+  int group_m;   // SRK_GROUP_M (0 = by tile shape): tile rows per swizzle group
+  int splits;    // SRK_GEMM_SPLITS (0 = by shape): the K split of batch-1 launches
+  int waves;     // SRK_GEMM_WAVES (0 = by transposes): waves of gemm_f32_kernel below the 256-row tile
+  int glds;      // SRK_GEMM_GLDS (default 1): gemm_f32_kernel's LDS-DMA staging, 0 = through registers
+  int lp_cfg;    // SRK_LP_CFG (0 = by shape): gemm_lp_kernel's tile configuration (lp_variant)
+  int h16_cfg;   // SRK_H16_CFG (0 = by shape): gemm_h16_kernel's tile configuration (h16_variant), 5 = gemm_g16_kernel
+  int tile;      // SRK_GEMM_TILE (0 = by shape): 256 = gemm_f32_kernel's 256 x 128 tile always, else never
 };
-Scratch g_scratch[64];
-std::mutex g_scratch_mu;
 
-int get_scratch(size_t floats, float** out) {
-  int dev = 0;
-  SRK_CHECK_HIP(hipGetDevice(&dev));
-  SRK_REQUIRE(dev >= 0 && dev < 64, SRK_ERR_INVALID, "device out of range");
-  std::lock_guard<std::mutex> lk(g_scratch_mu);
-  Scratch& s = g_scratch[dev];
-  if (s.floats < floats) {   // grow-only: steady state never allocates
-    if (s.p) {
-      SRK_CHECK_HIP(hipDeviceSynchronize());
-      SRK_CHECK_HIP(hipFree(s.p));
-      s.p = nullptr;
-    }
-    const size_t want = floats + floats / 4;
-    SRK_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&s.p), want * sizeof(float)));
-    g_scratch_gen.fetch_add(1);
-    s.floats = want;
-  }
-  *out = s.p;
-  return SRK_OK;
+// 32-bit buffer byte offsets bound the operands of the buffer-addressed kernels.  gemm_lp_kernel (VEC) and the
+// 16-bit-operand kernels clamp every index into the operand, so an extent may be anything below 2^31 B;
+// gemm_p32_kernel reads a K tail or an edge row as an offset PAST its descriptor's 0x7ffffff0 records (zero
+// fill), so its operands must end far enough below that for those offsets to stay in 32 bits.
+constexpr double kExtBuf = 2147483648.0, kExtP32 = 2147483000.0;
+
+enum GemmFamily { kFamNone, kFamSkinny, kFamF32, kFamLp, kFamH16, kFamG16, kFamP32 };
+using TileFn = void (*)(KernelArgs);
+using SkinnyFn = void (*)(GemmDesc);
+
+// Everything one gemm_f32 call launches, decided from the descriptor alone (no device is touched).
+struct GemmPlan {
+  GemmFamily family = kFamNone;   // kFamNone: an empty product, nothing to launch
+  int skinny = -1;                // kFamSkinny: 0 skinny_n, 1 skinny_m, 2 skinny_k
+  int prec = kPrecF32;            // the operand precision the launch runs at
+  int bm = 0, bn = 0, bk = 0, nw = 0, per_cu = 1;   // tile, waves launched, resident workgroups per CU
+  int waves = 0;                  // gemm_f32_kernel: the wave count its detail string states
+  bool vec = false, gl = false, f16 = false, streamk = false;
+  TileFn kernel = nullptr;        // the family's instantiation for (ta, tb) and the fields above
+  SkinnyFn skinny_kernel = nullptr;
+  dim3 grid, block;               // the batch rides on grid.z (gemm_f32 / gemm_lp_kernel) or grid.y (ping-pong kernels)
+  KernelArgs ka{};                // tiles, nblk, group_m, remap, kchunk, sk_wgs, sk_ki (gemm_launch adds d and the pointers)
+  int splits = 1;
+  size_t slab_floats = 0, rs_floats = 0, sk_floats = 0;   // scratch: split-K slabs | row-sum partials | stream-K slab
+  int reduce = 0;                 // after a split launch: 0 none, 1 splitk_reduce_kernel, 4 splitk_reduce4_kernel
+  bool rowsum_reduce = false;     // ... followed by rowsum_reduce_kernel
+  const char* name = "";          // profiler category, flops and algorithmic HBM bytes
+  double flops = 0.0, bytes = 0.0;
+  double ext_a = 0.0, ext_b = 0.0;   // byte extents of one batch entry's operands
+};
+
+// The four (ta, tb) cases, once: f(std::bool_constant<ta>, std::bool_constant<tb>).
+template <class F>
+auto with_trans(bool ta, bool tb, F f) {
+  if (!ta && !tb) return f(std::false_type{}, std::false_type{});
+  if (!ta && tb) return f(std::false_type{}, std::true_type{});
+  if (ta && !tb) return f(std::true_type{}, std::false_type{});
+  return f(std::true_type{}, std::true_type{});
 }
 
-// Resident workgroups per CU for the 256-thread, 2 x (BK x BM + BK x BN) fp32 LDS tile kernels.
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v && *v ? atoi(v) : dflt;
+// One instantiation of a tile family: the kernel with its tile, waves and resident workgroups per CU.
+struct Variant {
+  TileFn kernel;
+  int bm, bn, nw, per_cu;
+};
+
+template <int RND>
+SkinnyFn skinny_variant(int kind, bool ta, bool tb) {
+  if (kind == 0) return tb ? skinny_n_kernel<RND, true> : skinny_n_kernel<RND, false>;
+  if (kind == 1) return ta ? skinny_m_kernel<RND, true> : skinny_m_kernel<RND, false>;
+  return ta ? skinny_k_kernel<RND, true> : skinny_k_kernel<RND, false>;
 }
 
-// Grid, split-K and scratch for one launch of a BM x BN x BK tile kernel with `per_cu` resident
-// workgroups per CU; fills ka and returns the split count (tile::choose_splits).
-// split_batched: the kernel handles split-K slabs of batched launches ([batch][splits][M][N]; the
-// ping-pong kernels); the others split only batch-1 launches.
-int plan_launch(const GemmDesc& d, int BM, int BN, int BK, int per_cu, KernelArgs& ka, int* splits_out,
-                bool allow_split = true, bool split_batched = false) {
-  const int64_t tm = (d.M + BM - 1) / BM, tn = (d.N + BN - 1) / BN;
-  SRK_REQUIRE(tm * tn <= (INT32_MAX >> 5) && d.batch <= 65535, SRK_ERR_INVALID, "gemm: grid too large");
-  static const int remap = env_int("SRK_GEMM_REMAP", 1);
-  const int64_t slots = (int64_t)kCUs * per_cu;
-  ka = KernelArgs{};
-  ka.d = d;
-  ka.tiles_m = (int)tm;
-  ka.tiles_n = (int)tn;
-  ka.tiles = (int)(tm * tn);
-  // tile rows per swizzle group: an XCD runs ~32 x per_cu tiles at once out of a contiguous run of
-  // the grouped order (XCD remap), i.e. g rows x (32 per_cu / g) columns of tiles, whose distinct
-  // operand panels (g BM + 32 per_cu BN / g rows of K) its 4 MB L2 must hold; g = sqrt(32 per_cu
-  // BN / BM) minimises them (256 x 128 tiles: 4, was 8 — 8 A panels of 1 MB re-read per round)
-  static const int group_env = env_int("SRK_GROUP_M", 0);   // A/B measurements
-  ka.group_m = group_env > 0 ? group_env
-                             : std::max(1, (int)std::lround(std::sqrt(32.0 * per_cu * BN / (double)BM)));
-  ka.remap = remap;
-  // Split K when the output grid leaves resident slots idle and K is long (tile::choose_splits).
-  const int pb = std::max(d.batch, d.plan_batch);   // the batch the plan is made for (GemmDesc::plan_batch)
-  const bool can_split = allow_split && !d.no_split && (pb == 1 || split_batched);
-  int splits = can_split ? choose_splits(tm * tn * pb, d.K, BK, slots, 16) : 1;
-  static const int splits_env = env_int("SRK_GEMM_SPLITS", 0);   // A/B measurements only
-  if (splits_env > 0 && d.batch == 1 && d.K >= (int64_t)splits_env * 4 * BK) splits = splits_env;
-  ka.kchunk = splits > 1 ? ((d.K + splits - 1) / splits + BK - 1) / BK * BK : std::max<int64_t>(d.K, 1);
-  if (splits > 1) splits = (int)((d.K + ka.kchunk - 1) / ka.kchunk);
-  ka.nblk = ka.tiles * splits;
-  if (splits > 1) {
-    float* scratch = nullptr;
-    const size_t need = (size_t)d.batch * splits * (d.M * d.N + (d.rowsum ? d.M : 0));
-    if (int rc = get_scratch(need, &scratch)) return rc;
-    ka.partial = scratch;
-    ka.rs_partial = d.rowsum ? scratch + (size_t)d.batch * splits * d.M * d.N : nullptr;
-  }
-  *splits_out = splits;
-  return SRK_OK;
-}
-
-// After a split launch: the deterministic slab reduction (+ epilogue) and the row-sum reduction.
-int finish_splits(const GemmDesc& d, const KernelArgs& ka, int splits, hipStream_t s) {
-  SRK_CHECK_HIP(hipGetLastError());
-  if (splits > 1) {
-    const int64_t n = d.M * d.N;
-    const bool vec4 = d.N % 4 == 0 && d.ldc % 4 == 0 && (uintptr_t)d.C % 16 == 0 && d.sC % 4 == 0 &&
-                      (d.bias_mode != 1 || (uintptr_t)d.bias % 16 == 0);
-    if (vec4)
-      hipLaunchKernelGGL(splitk_reduce4_kernel, dim3((unsigned)((n / 4 + 255) / 256), (unsigned)d.batch), dim3(256), 0,
-                         s, d, ka.partial, splits);
-    else
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)d.batch), dim3(256), 0, s, d,
-                         ka.partial, splits);
-    if (d.rowsum)
-      hipLaunchKernelGGL(rowsum_reduce_kernel, dim3((unsigned)((d.M + 255) / 256), (unsigned)d.batch), dim3(256), 0, s,
-                         d.rowsum, d.rowsum_beta, ka.rs_partial, d.M, splits, d.sRS);
-    SRK_CHECK_HIP(hipGetLastError());
-  }
-  return SRK_OK;
-}
-
-template <bool TA, bool TB, int BM, int BN, int BK>
-int launch(const GemmDesc& d, hipStream_t s, bool vec) {
-  constexpr int lds = 2 * 4 * (Img<!TA, BM, BK>::FLOATS + Img<TB, BN, BK>::FLOATS);
+// gemm_f32_kernel: 256 x 128 (8 waves), 128 x 128 (8 or 4 waves) or 64 x 64 (4 waves), BK 32; per CU what 160 KB of
+// LDS hold of its 2 x (BK x BM + BK x BN) fp32 images, at most 8.
+template <bool TA, bool TB, int BM, int BN, int NW>
+Variant f32_tile(bool vec, bool gl) {
+  constexpr int lds = 2 * 4 * (Img<!TA, BM, 32>::FLOATS + Img<TB, BN, 32>::FLOATS);
   constexpr int per_cu0 = (160 * 1024) / lds < 8 ? (160 * 1024) / lds : 8;
-  constexpr int per_cu = per_cu0 > 0 ? per_cu0 : 1;
-  KernelArgs ka;
-  int splits = 1;
-  if (int rc = plan_launch(d, BM, BN, BK, per_cu, ka, &splits)) return rc;
-  ProfScope prof("gemm_f32", s, 2.0 * (double)d.M * (double)d.N * (double)d.K * d.batch);
-  prof.bytes(gemm_bytes(d, 4));
-  // 8 waves (4 per SIMD at 2 workgroups / CU) cover the k-tile staging + barrier phases better
-  // (measured: weight-gradient GEMMs +4..17 %); the x W^T projection shape keeps 4.
-  static const int waves_env = env_int("SRK_GEMM_WAVES", 0);
-  const int waves = BM == 256 ? 8 : (waves_env ? waves_env : ((!TA && TB) ? 4 : 8));
-  prof.detail("gemm_f32_kernel<%c%c,%dx%d,%dw> %lldx%lldx%lld b%lld s%d", TA ? 'T' : 'N', TB ? 'T' : 'N', BM, BN, waves,
-              (long long)d.M, (long long)d.N, (long long)d.K, (long long)d.batch, splits);
-  const dim3 grid((unsigned)ka.nblk, 1, (unsigned)d.batch);
-  // LDS-DMA staging (global_load_lds_dwordx4) whenever the 16-B vector conditions hold
-  static const int glds_env = env_int("SRK_GEMM_GLDS", 1);
-  const bool gl = vec && glds_env != 0;
-  bool done = false;
-  if constexpr (BN >= 128) {
-    if (waves == 8) {
-      if (gl) hipLaunchKernelGGL((gemm_f32_kernel<TA, TB, BM, BN, BK, true, 8, true>), grid, dim3(512), 0, s, ka);
-      else if (vec) hipLaunchKernelGGL((gemm_f32_kernel<TA, TB, BM, BN, BK, true, 8>), grid, dim3(512), 0, s, ka);
-      else hipLaunchKernelGGL((gemm_f32_kernel<TA, TB, BM, BN, BK, false, 8>), grid, dim3(512), 0, s, ka);
-      done = true;
-    }
-  }
-  if constexpr (BM != 256) {
-    if (!done) {
-      if (gl) hipLaunchKernelGGL((gemm_f32_kernel<TA, TB, BM, BN, BK, true, 4, true>), grid, dim3(256), 0, s, ka);
-      else if (vec) hipLaunchKernelGGL((gemm_f32_kernel<TA, TB, BM, BN, BK, true, 4>), grid, dim3(256), 0, s, ka);
-      else hipLaunchKernelGGL((gemm_f32_kernel<TA, TB, BM, BN, BK, false, 4>), grid, dim3(256), 0, s, ka);
-    }
-  }
-  return finish_splits(d, ka, splits, s);
+  return {gl    ? gemm_f32_kernel<TA, TB, BM, BN, 32, true, NW, true>
+          : vec ? gemm_f32_kernel<TA, TB, BM, BN, 32, true, NW>
+                : gemm_f32_kernel<TA, TB, BM, BN, 32, false, NW>,
+          BM, BN, NW, per_cu0 > 0 ? per_cu0 : 1};
+}
+template <bool TA, bool TB>
+Variant f32_variant(int bm, int waves, bool vec, bool gl) {
+  if (bm == 256) return f32_tile<TA, TB, 256, 128, 8>(vec, gl);
+  if (bm == 128) return waves == 8 ? f32_tile<TA, TB, 128, 128, 8>(vec, gl) : f32_tile<TA, TB, 128, 128, 4>(vec, gl);
+  return f32_tile<TA, TB, 64, 64, 4>(vec, gl);
 }
 
-template <bool TA, bool TB, int BM, int BN, int NW, int PF>
-int launch_lp_cfg(const GemmDesc& d, hipStream_t s, bool vec, bool f16) {
-  constexpr int per_cu = lp_per_cu<BM, BN>();
-  // buffer-instruction byte offsets are 32-bit: VEC also needs both operands' extents < 2^31 B
-  const double ext_a = (double)(d.ta ? d.K : d.M) * d.lda * 4, ext_b = (double)(d.tb ? d.N : d.K) * d.ldb * 4;
-  if (ext_a >= 2147483648.0 || ext_b >= 2147483648.0 || d.batch != 1) vec = false;
-  KernelArgs ka;
-  int splits = 1;
-  if (int rc = plan_launch(d, BM, BN, kLpBK, per_cu, ka, &splits)) return rc;
-  ProfScope prof(f16 ? "gemm_f16" : "gemm_bf16", s, 2.0 * (double)d.M * (double)d.N * (double)d.K * d.batch);
-  prof.bytes(gemm_bytes(d, 4));   // fp32 operands in HBM, rounded on chip
-  prof.detail("gemm_lp_kernel<%c%c,%dx%d> %lldx%lldx%lld s%d", TA ? 'T' : 'N', TB ? 'T' : 'N', BM, BN, (long long)d.M,
-              (long long)d.N, (long long)d.K, splits);
-  const dim3 grid((unsigned)ka.nblk, 1, (unsigned)d.batch), block(NW * 64);
-  if (f16) {
-    if (vec) hipLaunchKernelGGL((gemm_lp_kernel<TA, TB, BM, BN, NW, true, true, PF>), grid, block, 0, s, ka);
-    else hipLaunchKernelGGL((gemm_lp_kernel<TA, TB, BM, BN, NW, false, true, PF>), grid, block, 0, s, ka);
-  } else {
-    if (vec) hipLaunchKernelGGL((gemm_lp_kernel<TA, TB, BM, BN, NW, true, false, PF>), grid, block, 0, s, ka);
-    else hipLaunchKernelGGL((gemm_lp_kernel<TA, TB, BM, BN, NW, false, false, PF>), grid, block, 0, s, ka);
-  }
-  return finish_splits(d, ka, splits, s);
-}
-
-// Tile configuration of the bf16 / fp16 GEMM (SRK_LP_CFG overrides the choice for A/B measurements):
+// Tile configuration of the bf16 / fp16 GEMM on fp32 operands (SRK_LP_CFG overrides the choice for A/B measurements):
 //   1: 128 x 128, 4 waves, 1 k-tile of register prefetch (2 workgroups / CU)
 //   2: 128 x 128, 4 waves, 2 k-tiles in flight
 //   3: 256 x 128, 8 waves (4 x 2, 64 x 64 each), 1 k-tile (1 workgroup / CU)
 //   4: 256 x 128, 8 waves, 2 k-tiles in flight
 //   5: 128 x 128, 8 waves (2 x 4, 64 x 32 each), 2 k-tiles in flight
+template <bool TA, bool TB, int BM, int BN, int NW, int PF>
+Variant lp_tile(bool vec, bool f16) {
+  return {f16 ? (vec ? gemm_lp_kernel<TA, TB, BM, BN, NW, true, true, PF> : gemm_lp_kernel<TA, TB, BM, BN, NW, false, true, PF>)
+              : (vec ? gemm_lp_kernel<TA, TB, BM, BN, NW, true, false, PF> : gemm_lp_kernel<TA, TB, BM, BN, NW, false, false, PF>),
+          BM, BN, NW, lp_per_cu<BM, BN>()};
+}
 template <bool TA, bool TB>
-int launch_lp(const GemmDesc& d, hipStream_t s, bool vec, bool f16) {
-  static const int cfg_env = env_int("SRK_LP_CFG", 0);
-  int cfg = cfg_env;
-  // measured (profiles/r01zf_gemm_bench_bf16_cfg*.txt): 256 x 128 tiles win whenever an operand is
-  // row-contiguous (dx, dW: 12-25 %), the 128 x 128 tile on the x W^T projection (both k-contiguous)
-  if (!cfg) cfg = (d.M >= 1024 && !(!TA && TB)) ? 3 : 1;
+Variant lp_variant(int cfg, bool vec, bool f16) {
   switch (cfg) {
-    case 2: return launch_lp_cfg<TA, TB, 128, 128, 4, 2>(d, s, vec, f16);
-    case 3: return launch_lp_cfg<TA, TB, 256, 128, 8, 1>(d, s, vec, f16);
-    case 4: return launch_lp_cfg<TA, TB, 256, 128, 8, 2>(d, s, vec, f16);
-    case 5: return launch_lp_cfg<TA, TB, 128, 128, 8, 2>(d, s, vec, f16);
-    default: return launch_lp_cfg<TA, TB, 128, 128, 4, 1>(d, s, vec, f16);
+    case 2: return lp_tile<TA, TB, 128, 128, 4, 2>(vec, f16);
+    case 3: return lp_tile<TA, TB, 256, 128, 8, 1>(vec, f16);
+    case 4: return lp_tile<TA, TB, 256, 128, 8, 2>(vec, f16);
+    case 5: return lp_tile<TA, TB, 128, 128, 8, 2>(vec, f16);
+    default: return lp_tile<TA, TB, 128, 128, 4, 1>(vec, f16);
   }
 }
 
+// gemm_h16_kernel (16-bit operands in memory, register-staged): 3 = 256 x 128, 4 = 256 x 256 (8 waves), else 128 x 128
 template <bool TA, bool TB, int BM, int BN, int NW>
-int launch_h16_cfg(const GemmDesc& d, hipStream_t s, bool f16) {
-  constexpr int per_cu = h16_per_cu<TA, TB, BM, BN>();
-  KernelArgs ka;
-  int splits = 1;
-  if (int rc = plan_launch(d, BM, BN, kLpBK, per_cu, ka, &splits)) return rc;
-  ProfScope prof(f16 ? "gemm_f16" : "gemm_bf16", s, 2.0 * (double)d.M * (double)d.N * (double)d.K);
-  prof.bytes(gemm_bytes(d, 2));
-  prof.detail("gemm_h16_kernel<%c%c,%dx%d> %lldx%lldx%lld s%d", TA ? 'T' : 'N', TB ? 'T' : 'N', BM, BN, (long long)d.M,
-              (long long)d.N, (long long)d.K, splits);
-  const dim3 grid((unsigned)ka.nblk), block(NW * 64);
-  if (f16) hipLaunchKernelGGL((gemm_h16_kernel<TA, TB, BM, BN, NW, true>), grid, block, 0, s, ka);
-  else hipLaunchKernelGGL((gemm_h16_kernel<TA, TB, BM, BN, NW, false>), grid, block, 0, s, ka);
-  return finish_splits(d, ka, splits, s);
+Variant h16_tile(bool f16) {
+  return {f16 ? gemm_h16_kernel<TA, TB, BM, BN, NW, true> : gemm_h16_kernel<TA, TB, BM, BN, NW, false>, BM, BN, NW,
+          h16_per_cu<TA, TB, BM, BN>()};
 }
-
 template <bool TA, bool TB>
-int launch_g16(const GemmDesc& d, hipStream_t s, bool f16) {
-  KernelArgs ka;
-  int splits = 1;
-  // split K only when the 256 x 256 output grid leaves more than half of the CUs idle: the slabs
-  // (M x N fp32 per split, written and re-read) cost more than a partly filled round otherwise
-  const int64_t tiles = ((d.M + 255) / 256) * ((d.N + 255) / 256) * d.batch;
-  if (int rc = plan_launch(d, 256, 256, kG16BK, 1, ka, &splits, tiles * 2 < kCUs, true)) return rc;
-  ProfScope prof(f16 ? "gemm_f16" : "gemm_bf16", s, 2.0 * (double)d.M * (double)d.N * (double)d.K * d.batch);
-  prof.bytes(gemm_bytes(d, 2));
-  prof.detail("gemm_g16_kernel<%c%c> %lldx%lldx%lld b%d s%d", TA ? 'T' : 'N', TB ? 'T' : 'N', (long long)d.M,
-              (long long)d.N, (long long)d.K, d.batch, splits);
-  const dim3 grid((unsigned)ka.nblk, (unsigned)d.batch), block(512);
-  if (f16) hipLaunchKernelGGL((gemm_g16_kernel<TA, TB, true>), grid, block, 0, s, ka);
-  else hipLaunchKernelGGL((gemm_g16_kernel<TA, TB, false>), grid, block, 0, s, ka);
-  return finish_splits(d, ka, splits, s);
+Variant h16_variant(int cfg, bool f16) {
+  if (cfg == 3) return h16_tile<TA, TB, 256, 128, 8>(f16);
+  if (cfg == 4) return h16_tile<TA, TB, 256, 256, 8>(f16);
+  return h16_tile<TA, TB, 128, 128, 4>(f16);
 }
 
-template <bool TA, bool TB>
-int launch_h16(const GemmDesc& d, hipStream_t s, bool f16) {
-  static const int cfg_env = env_int("SRK_H16_CFG", 0);
-  // the LDS-DMA ping-pong kernel wherever its 256 x 256 tile fills the chip (srk option overrides)
-  const int kern = g_opt_gemm16_kernel ? g_opt_gemm16_kernel : (d.M >= 1024 && d.N >= 256 ? 2 : 1);
-  if (kern == 2 || cfg_env == 5 || d.batch > 1) return launch_g16<TA, TB>(d, s, f16);   // only g16 is batched
-  // measured (profiles/r01zk_gemm_h16_cfg*.txt): 256 x 256 on x W^T and on the weight gradients
-  // (TA != TB: gi 143 vs 148 us, dW_ih 128 vs 137), 256 x 128 on dx (204 tiles of 256 x 256 leave
-  // CUs idle: 255 vs 147 us), 128 x 128 below 1024 rows
-  const int cfg = cfg_env ? cfg_env : d.M < 1024 ? 1 : (TA != TB && d.N >= 256) ? 4 : 3;
-  if (cfg == 3) return launch_h16_cfg<TA, TB, 256, 128, 8>(d, s, f16);
-  if (cfg == 4) return launch_h16_cfg<TA, TB, 256, 256, 8>(d, s, f16);
-  return launch_h16_cfg<TA, TB, 128, 128, 4>(d, s, f16);
-}
-
-template <bool TA, bool TB>
-int launch_p32(const GemmDesc& d, hipStream_t s) {
-  KernelArgs ka;
-  int splits = 1;
-  const int pb = std::max(d.batch, d.plan_batch);
-  const int64_t tiles = ((d.M + 255) / 256) * ((d.N + 255) / 256) * pb;
-  const int64_t ki = (d.K + kP32BK - 1) / kP32BK;
-  // stream-K where one round of 256 x 256 tiles leaves CUs idle but covers at least half of them
-  // (dx of the BiGRU layers: 204 tiles on 256 CUs), K long enough to split
-  const bool streamk = g_opt_gemm_streamk && pb == 1 && !d.no_split && !d.rowsum && tiles < kCUs && tiles * 2 >= kCUs && ki >= 32;
-  if (int rc = plan_launch(d, 256, 256, kP32BK, 1, ka, &splits, !streamk && tiles * 2 < kCUs, true)) return rc;
-  if (streamk) {
-    ka.sk_wgs = kCUs;
-    ka.sk_ki = (int)ki;
-    ka.nblk = kCUs;
-    if (int rc = get_scratch((size_t)3 * d.M * d.N, &ka.sk_slab)) return rc;   // <= 3 runs per tile (tiles >= W / 2)
-  }
-  ProfScope prof("gemm_f32", s, 2.0 * (double)d.M * (double)d.N * (double)d.K * d.batch);
-  prof.bytes(gemm_bytes(d, 4));
-  prof.detail("gemm_p32_kernel<%c%c> %lldx%lldx%lld b%d s%d%s", TA ? 'T' : 'N', TB ? 'T' : 'N', (long long)d.M,
-              (long long)d.N, (long long)d.K, d.batch, splits, streamk ? " streamk" : "");
-  hipLaunchKernelGGL((gemm_p32_kernel<TA, TB>), dim3((unsigned)ka.nblk, (unsigned)d.batch), dim3(512), 0, s, ka);
-  if (streamk) hipLaunchKernelGGL(sk_fixup_kernel, dim3((unsigned)ka.tiles * kSkFixupSlices), dim3(256), 0, s, ka);
-  return finish_splits(d, ka, splits, s);
-}
-
-template <bool TA, bool TB>
-int dispatch_tile(const GemmDesc& d, hipStream_t s, bool vec) {
-  const int prec = d.prec >= 0 ? d.prec : matmul_prec();
-  if (prec != kPrecF32) return launch_lp<TA, TB>(d, s, vec, prec == kPrecF16);
-  // the LDS-DMA ping-pong kernel where a 256 x 256 grid fills the chip (16-B units, 32-bit buffer
-  // offsets, batch 1); srk option gemm32_kernel: 1 register-staged, 2 ping-pong
-  const double ext_a = (double)(d.ta ? d.K : d.M) * d.lda * 4, ext_b = (double)(d.tb ? d.N : d.K) * d.ldb * 4;
-  const bool p32_ok = vec && ext_a < 2147483000.0 && ext_b < 2147483000.0;
-  // measured (tools/gemm_bench.py, cfg2 shapes): ping-pong 6-7 % faster on dx (NN) and dW_ih (TN),
-  // 8 % slower on the x W^T projection (NT) and on the 12-tile dW_hh grid (split 16); batched
-  // launches (the BiGRU's two dW_hh) and row sums over a batch only exist on the ping-pong kernel
-  const int kern32 = g_opt_gemm32_kernel ? g_opt_gemm32_kernel
-                                         : (!TB && ((d.M >= 2048 && d.N >= 1024) || d.batch > 1 || d.plan_batch > 1) ? 2 : 1);
-  SRK_REQUIRE(!d.rowsum || d.batch == 1 || (p32_ok && kern32 == 2), SRK_ERR_INVALID,
-              "gemm: batched row sums need the fp32 ping-pong kernel (16-B operand rows)");
-  if (p32_ok && kern32 == 2) return launch_p32<TA, TB>(d, s);
-  // 256 x 128 tiles (one 8-wave workgroup per CU, 110 KB of LDS) halve the L2 -> CU operand
-  // traffic per flop of the 128 x 128 tile; used when the grid still fills the chip several times
-  static const int tile_env = env_int("SRK_GEMM_TILE", 0);
-  const int64_t t256 = ((d.M + 255) / 256) * ((d.N + 127) / 128) * d.batch;
-  const bool big = tile_env ? tile_env == 256 : (d.M >= 2048 && d.N >= 128 && d.K >= 256 && (t256 >= 512 || d.K >= 4096));
-  if (big) return launch<TA, TB, 256, 128, 32>(d, s, vec);
-  const int64_t big_tiles = ((d.M + 127) / 128) * ((d.N + 127) / 128) * d.batch;
-  if (d.M > 64 && d.N > 64 && (big_tiles >= 64 || d.K >= 2048)) return launch<TA, TB, 128, 128, 32>(d, s, vec);
-  return launch<TA, TB, 64, 64, 32>(d, s, vec);
-}
-
-}  // namespace
-
-bool gemm_f32_batched_rowsum_ok(const GemmDesc& d) {
-  // mirrors gemm_f32 -> dispatch_tile: batched row sums exist only on the fp32-operand ping-pong
-  // kernel (fp32 precision, 16-B operand rows, 32-bit buffer extents, not overridden to kernel 1)
-  const int prec = d.prec >= 0 ? d.prec : matmul_prec();
-  if (prec != kPrecF32 || d.A16 || d.B16 || d.tb || g_opt_gemm32_kernel == 1) return false;
-  const bool kc_operand = !d.ta || d.tb;
-  const bool vec = (d.lda % 4 == 0) && ((uintptr_t)d.A % 16 == 0) && (d.sA % 4 == 0) && (d.ldb % 4 == 0) &&
-                   ((uintptr_t)d.B % 16 == 0) && (d.sB % 4 == 0) && (!kc_operand || d.K % 4 == 0) &&
-                   (!d.ta || d.M % 4 == 0) && (d.tb || d.N % 4 == 0);
-  const double ext_a = (double)(d.ta ? d.K : d.M) * d.lda * 4, ext_b = (double)(d.tb ? d.N : d.K) * d.ldb * 4;
-  // a batched launch spans batch - 1 strides past the first operand
-  const double span_a = ext_a + (double)(d.batch - 1) * d.sA * 4, span_b = ext_b + (double)(d.batch - 1) * d.sB * 4;
-  return vec && span_a < 2147483000.0 && span_b < 2147483000.0;
-}
-
-int gemm_f32(const GemmDesc& d, hipStream_t s) {
+// The plan of gemm_f32(d): argument checks, kernel family and variant, grid, K split / stream-K, scratch, the
+// reduction that follows and the profiler record.  Pure host arithmetic on d, the srk options and GemmEnv.
+int gemm_plan(const GemmDesc& d, GemmPlan& p) {
+  static const GemmEnv env = [] {
+    auto knob = [](const char* name, int dflt) {
+      const char* v = getenv(name);
+      return v && *v ? atoi(v) : dflt;
+    };
+    return GemmEnv{knob("SRK_GEMM_REMAP", 1), knob("SRK_GROUP_M", 0),  knob("SRK_GEMM_SPLITS", 0), knob("SRK_GEMM_WAVES", 0),
+                   knob("SRK_GEMM_GLDS", 1),  knob("SRK_LP_CFG", 0),   knob("SRK_H16_CFG", 0),     knob("SRK_GEMM_TILE", 0)};
+  }();
+  p = GemmPlan{};
   SRK_REQUIRE(d.M >= 0 && d.N >= 0 && d.K >= 0 && d.batch >= 1, SRK_ERR_INVALID, "gemm: bad shape");
   if (d.M == 0 || d.N == 0) return SRK_OK;
-  if (d.A16 || d.B16) {   // 16-bit operands in memory
-    const int prec = d.prec >= 0 ? d.prec : matmul_prec();
+
+  const int prec = d.prec >= 0 ? d.prec : matmul_prec();
+  const bool ops16 = d.A16 || d.B16;   // 16-bit operands in memory
+  const int esz = ops16 ? 2 : 4;
+  const double ext_a = (double)(d.ta ? d.K : d.M) * d.lda * esz, ext_b = (double)(d.tb ? d.N : d.K) * d.ldb * esz;
+  const int pb = std::max(d.batch, d.plan_batch);   // the batch the plan is made for (GemmDesc::plan_batch)
+  p.prec = prec;
+  p.f16 = prec == kPrecF16;
+  p.ext_a = ext_a;
+  p.ext_b = ext_b;
+  p.name = prec == kPrecBF16 ? "gemm_bf16" : prec == kPrecF16 ? "gemm_f16" : "gemm_f32";
+  p.flops = 2.0 * (double)d.M * (double)d.N * (double)d.K * d.batch;
+  p.bytes = gemm_bytes(d, esz);   // lp / skinny kernels: fp32 operands in HBM, rounded on chip
+
+  // Grid, K split and scratch of a v.bm x v.bn x BK tile kernel with v.per_cu resident workgroups per CU.
+  // split_batched: the kernel handles split-K slabs of batched launches ([batch][splits][M][N]; the
+  // ping-pong kernels); the others split only batch-1 launches.
+  auto tiles_and_split = [&](GemmFamily family, const Variant& v, int BK, bool allow_split, bool split_batched) -> int {
+    const int BM = v.bm, BN = v.bn;
+    const int64_t tm = (d.M + BM - 1) / BM, tn = (d.N + BN - 1) / BN;
+    SRK_REQUIRE(tm * tn <= (INT32_MAX >> 5) && d.batch <= 65535, SRK_ERR_INVALID, "gemm: grid too large");
+    p.family = family;
+    p.kernel = v.kernel;
+    p.bm = BM; p.bn = BN; p.bk = BK; p.nw = v.nw; p.per_cu = v.per_cu;
+    const int64_t slots = (int64_t)kCUs * v.per_cu;
+    KernelArgs& ka = p.ka;
+    ka.tiles_m = (int)tm;
+    ka.tiles_n = (int)tn;
+    ka.tiles = (int)(tm * tn);
+    // tile rows per swizzle group: an XCD runs ~32 x per_cu tiles at once out of a contiguous run of
+    // the grouped order (XCD remap), i.e. g rows x (32 per_cu / g) columns of tiles, whose distinct
+    // operand panels (g BM + 32 per_cu BN / g rows of K) its 4 MB L2 must hold; g = sqrt(32 per_cu
+    // BN / BM) minimises them (256 x 128 tiles: 4, was 8 — 8 A panels of 1 MB re-read per round)
+    ka.group_m = env.group_m > 0 ? env.group_m
+                                 : std::max(1, (int)std::lround(std::sqrt(32.0 * v.per_cu * BN / (double)BM)));
+    ka.remap = env.remap;
+    // Split K when the output grid leaves resident slots idle and K is long (tile::choose_splits).
+    const bool can_split = allow_split && !d.no_split && (pb == 1 || split_batched);
+    int splits = can_split ? choose_splits(tm * tn * pb, d.K, BK, slots, 16) : 1;
+    if (env.splits > 0 && d.batch == 1 && d.K >= (int64_t)env.splits * 4 * BK) splits = env.splits;
+    ka.kchunk = splits > 1 ? ((d.K + splits - 1) / splits + BK - 1) / BK * BK : std::max<int64_t>(d.K, 1);
+    if (splits > 1) splits = (int)((d.K + ka.kchunk - 1) / ka.kchunk);
+    ka.nblk = ka.tiles * splits;
+    p.splits = splits;
+    if (splits > 1) {   // the deterministic slab reduction (+ epilogue) and the row-sum reduction follow
+      p.slab_floats = (size_t)d.batch * splits * d.M * d.N;
+      p.rs_floats = d.rowsum ? (size_t)d.batch * splits * d.M : 0;
+      const bool vec4 = d.N % 4 == 0 && d.ldc % 4 == 0 && (uintptr_t)d.C % 16 == 0 && d.sC % 4 == 0 &&
+                        (d.bias_mode != 1 || (uintptr_t)d.bias % 16 == 0);
+      p.reduce = vec4 ? 4 : 1;
+      p.rowsum_reduce = d.rowsum != nullptr;
+    }
+    return SRK_OK;
+  };
+  // 256 x 256 tiles of one batch entry (the ping-pong kernels' grid)
+  const int64_t tiles256 = ((d.M + 255) / 256) * ((d.N + 255) / 256);
+
+  if (ops16) {
     SRK_REQUIRE(d.A16 && d.B16 && d.C && prec != kPrecF32 && !d.rowsum && (d.batch == 1 || d.bias_mode == 0),
                 SRK_ERR_INVALID,
                 "gemm: 16-bit operands need both A16 / B16, a 16-bit precision and no row sums (no bias when batched)");
     SRK_REQUIRE(d.batch == 1 || (d.sA % 8 == 0 && d.sB % 8 == 0 && d.sC % 4 == 0), SRK_ERR_INVALID,
                 "gemm: batched 16-bit operands need 8-element strides");
-    const double ext_a = (double)(d.ta ? d.K : d.M) * d.lda * 2, ext_b = (double)(d.tb ? d.N : d.K) * d.ldb * 2;
     SRK_REQUIRE((uintptr_t)d.A16 % 16 == 0 && (uintptr_t)d.B16 % 16 == 0 && d.lda % 8 == 0 && d.ldb % 8 == 0 &&
                     ((d.ta && d.M % 8 == 0) || (!d.ta && d.K % 8 == 0)) &&
-                    ((d.tb && d.K % 8 == 0) || (!d.tb && d.N % 8 == 0)) && ext_a < 2147483648.0 &&
-                    ext_b < 2147483648.0,
+                    ((d.tb && d.K % 8 == 0) || (!d.tb && d.N % 8 == 0)) && ext_a < kExtBuf && ext_b < kExtBuf,
                 SRK_ERR_INVALID, "gemm: 16-bit operands need 16-B aligned rows of 8-element multiples");
     SRK_REQUIRE(d.K > 0, SRK_ERR_INVALID, "gemm: 16-bit operands need K > 0");
-    const bool f16 = prec == kPrecF16;
-    if (!d.ta && !d.tb) return launch_h16<false, false>(d, s, f16);
-    if (!d.ta && d.tb) return launch_h16<false, true>(d, s, f16);
-    if (d.ta && !d.tb) return launch_h16<true, false>(d, s, f16);
-    return launch_h16<true, true>(d, s, f16);
+    // the LDS-DMA ping-pong kernel wherever its 256 x 256 tile fills the chip (srk option overrides)
+    const int kern = g_opt_gemm16_kernel ? g_opt_gemm16_kernel : (d.M >= 1024 && d.N >= 256 ? 2 : 1);
+    if (kern == 2 || env.h16_cfg == 5 || d.batch > 1) {   // only g16 is batched
+      const TileFn k = with_trans(d.ta, d.tb, [&](auto ta, auto tb) -> TileFn {
+        return p.f16 ? gemm_g16_kernel<decltype(ta)::value, decltype(tb)::value, true>
+                     : gemm_g16_kernel<decltype(ta)::value, decltype(tb)::value, false>;
+      });
+      // split K only when the 256 x 256 output grid leaves more than half of the CUs idle: the slabs
+      // (M x N fp32 per split, written and re-read) cost more than a partly filled round otherwise
+      if (int rc = tiles_and_split(kFamG16, Variant{k, 256, 256, 8, 1}, kG16BK, tiles256 * d.batch * 2 < kCUs, true)) return rc;
+      p.grid = dim3((unsigned)p.ka.nblk, (unsigned)d.batch);
+    } else {
+      // measured (profiles/r01zk_gemm_h16_cfg*.txt): 256 x 256 on x W^T and on the weight gradients
+      // (TA != TB: gi 143 vs 148 us, dW_ih 128 vs 137), 256 x 128 on dx (204 tiles of 256 x 256 leave
+      // CUs idle: 255 vs 147 us), 128 x 128 below 1024 rows
+      const int cfg = env.h16_cfg ? env.h16_cfg : d.M < 1024 ? 1 : (d.ta != d.tb && d.N >= 256) ? 4 : 3;
+      const Variant v = with_trans(d.ta, d.tb, [&](auto ta, auto tb) {
+        return h16_variant<decltype(ta)::value, decltype(tb)::value>(cfg, p.f16);
+      });
+      if (int rc = tiles_and_split(kFamH16, v, kLpBK, true, false)) return rc;
+      p.grid = dim3((unsigned)p.ka.nblk);
+    }
+    p.block = dim3(p.nw * 64);
+    return SRK_OK;
   }
+
   SRK_REQUIRE(d.C && (d.K == 0 || (d.A && d.B)), SRK_ERR_INVALID, "gemm: null operand");
   SRK_REQUIRE(d.bias_mode == 0 || d.bias, SRK_ERR_INVALID, "gemm: bias_mode without bias");
-  if (const int kind = skinny_kind(d); kind >= 0) {   // one dimension <= 16: VALU kernels
-    const int prec = d.prec >= 0 ? d.prec : matmul_prec();
-    return prec == kPrecBF16 ? launch_skinny_rnd<1>(d, kind, s)
-           : prec == kPrecF16 ? launch_skinny_rnd<2>(d, kind, s) : launch_skinny_rnd<0>(d, kind, s);
+  // One dimension <= 16: the VALU skinny kernels.  Sizes keep each kernel's per-thread loop short and its
+  // streamed operand a few MB at most.
+  if (g_opt_gemm_skinny && d.batch == 1 && d.plan_batch <= 1 && d.K > 0) {
+    if (d.N <= 16 && !d.ta && d.M <= 65535 * 16 && d.M * d.K <= (int64_t)1 << 24) p.skinny = 0;
+    else if (d.M <= 16 && !d.tb && d.K <= 1024 && d.N * d.K <= (int64_t)1 << 24) p.skinny = 1;
+    else if (d.K <= 16 && !d.tb && d.M <= 65535 && d.M * d.N <= (int64_t)1 << 24) p.skinny = 2;
   }
-  SRK_REQUIRE(!d.rowsum || d.batch == 1 || d.prec == kPrecF32 || (d.prec < 0 && matmul_prec() == kPrecF32),
-              SRK_ERR_INVALID, "gemm: batched rowsum needs fp32 operands");
+  if (p.skinny >= 0) {
+    p.family = kFamSkinny;
+    p.skinny_kernel = prec == kPrecBF16  ? skinny_variant<1>(p.skinny, d.ta, d.tb)
+                      : prec == kPrecF16 ? skinny_variant<2>(p.skinny, d.ta, d.tb)
+                                         : skinny_variant<0>(p.skinny, d.ta, d.tb);
+    p.grid = p.skinny == 0   ? dim3((unsigned)d.M)
+             : p.skinny == 1 ? dim3((unsigned)((d.N + 63) / 64))
+                             : dim3((unsigned)((d.N + 255) / 256), (unsigned)d.M);
+    p.block = dim3(p.skinny == 1 ? 1024 : 256);
+    return SRK_OK;
+  }
+  SRK_REQUIRE(!d.rowsum || d.batch == 1 || prec == kPrecF32, SRK_ERR_INVALID, "gemm: batched rowsum needs fp32 operands");
   // 16-B loads need 16-B aligned rows, K % 4 == 0 when an operand is k-contiguous (a clamped k vector
   // stays inside the row) and,
   // along M / N (A when ta, B when !tb), a row count that is a multiple of 4 (a clamped vector is
@@ -2045,10 +1925,158 @@ int gemm_f32(const GemmDesc& d, hipStream_t s) {
   const bool vec = (d.lda % 4 == 0) && ((uintptr_t)d.A % 16 == 0) && (d.sA % 4 == 0) && (d.ldb % 4 == 0) &&
                    ((uintptr_t)d.B % 16 == 0) && (d.sB % 4 == 0) && (!kc_operand || d.K % 4 == 0) &&
                    (!d.ta || d.M % 4 == 0) && (d.tb || d.N % 4 == 0);
-  if (!d.ta && !d.tb) return dispatch_tile<false, false>(d, s, vec);
-  if (!d.ta && d.tb) return dispatch_tile<false, true>(d, s, vec);
-  if (d.ta && !d.tb) return dispatch_tile<true, false>(d, s, vec);
-  return dispatch_tile<true, true>(d, s, vec);
+
+  if (prec != kPrecF32) {   // fp32 operands rounded on chip
+    // buffer-instruction byte offsets are 32-bit: VEC also needs both operands' extents < 2^31 B
+    p.vec = vec && ext_a < kExtBuf && ext_b < kExtBuf && d.batch == 1;
+    // measured (profiles/r01zf_gemm_bench_bf16_cfg*.txt): 256 x 128 tiles win whenever an operand is
+    // row-contiguous (dx, dW: 12-25 %), the 128 x 128 tile on the x W^T projection (both k-contiguous)
+    const int cfg = env.lp_cfg ? env.lp_cfg : (d.M >= 1024 && !(!d.ta && d.tb)) ? 3 : 1;
+    const Variant v = with_trans(d.ta, d.tb, [&](auto ta, auto tb) {
+      return lp_variant<decltype(ta)::value, decltype(tb)::value>(cfg, p.vec, p.f16);
+    });
+    if (int rc = tiles_and_split(kFamLp, v, kLpBK, true, false)) return rc;
+    p.grid = dim3((unsigned)p.ka.nblk, 1, (unsigned)d.batch);
+    p.block = dim3(p.nw * 64);
+    return SRK_OK;
+  }
+
+  // the LDS-DMA ping-pong kernel where a 256 x 256 grid fills the chip (16-B units, 32-bit buffer
+  // offsets, batch 1); srk option gemm32_kernel: 1 register-staged, 2 ping-pong
+  const bool p32_ok = vec && ext_a < kExtP32 && ext_b < kExtP32;
+  // measured (tools/gemm_bench.py, cfg2 shapes): ping-pong 6-7 % faster on dx (NN) and dW_ih (TN),
+  // 8 % slower on the x W^T projection (NT) and on the 12-tile dW_hh grid (split 16); batched
+  // launches (the BiGRU's two dW_hh) and row sums over a batch only exist on the ping-pong kernel
+  const int kern32 = g_opt_gemm32_kernel ? g_opt_gemm32_kernel
+                                         : (!d.tb && ((d.M >= 2048 && d.N >= 1024) || d.batch > 1 || d.plan_batch > 1) ? 2 : 1);
+  SRK_REQUIRE(!d.rowsum || d.batch == 1 || (p32_ok && kern32 == 2), SRK_ERR_INVALID,
+              "gemm: batched row sums need the fp32 ping-pong kernel (16-B operand rows)");
+  if (p32_ok && kern32 == 2) {
+    const int64_t tiles = tiles256 * pb;
+    const int64_t ki = (d.K + kP32BK - 1) / kP32BK;
+    // stream-K where one round of 256 x 256 tiles leaves CUs idle but covers at least half of them
+    // (dx of the BiGRU layers: 204 tiles on 256 CUs), K long enough to split
+    p.streamk = g_opt_gemm_streamk && pb == 1 && !d.no_split && !d.rowsum && tiles < kCUs && tiles * 2 >= kCUs && ki >= 32;
+    const TileFn k = with_trans(d.ta, d.tb, [](auto ta, auto tb) -> TileFn {
+      return gemm_p32_kernel<decltype(ta)::value, decltype(tb)::value>;
+    });
+    if (int rc = tiles_and_split(kFamP32, Variant{k, 256, 256, 8, 1}, kP32BK, !p.streamk && tiles * 2 < kCUs, true)) return rc;
+    if (p.streamk) {
+      p.ka.sk_wgs = kCUs;
+      p.ka.sk_ki = (int)ki;
+      p.ka.nblk = kCUs;
+      p.sk_floats = (size_t)3 * d.M * d.N;   // <= 3 runs per tile (tiles >= W / 2)
+    }
+    p.vec = true;
+    p.grid = dim3((unsigned)p.ka.nblk, (unsigned)d.batch);
+    p.block = dim3(512);
+    return SRK_OK;
+  }
+
+  // 256 x 128 tiles (one 8-wave workgroup per CU, 110 KB of LDS) halve the L2 -> CU operand
+  // traffic per flop of the 128 x 128 tile; used when the grid still fills the chip several times
+  const int64_t t256 = ((d.M + 255) / 256) * ((d.N + 127) / 128) * d.batch;
+  const bool big = env.tile ? env.tile == 256 : (d.M >= 2048 && d.N >= 128 && d.K >= 256 && (t256 >= 512 || d.K >= 4096));
+  const int64_t big_tiles = ((d.M + 127) / 128) * ((d.N + 127) / 128) * d.batch;
+  const int bm = big ? 256 : (d.M > 64 && d.N > 64 && (big_tiles >= 64 || d.K >= 2048)) ? 128 : 64;
+  // 8 waves (4 per SIMD at 2 workgroups / CU) cover the k-tile staging + barrier phases better
+  // (measured: weight-gradient GEMMs +4..17 %); the x W^T projection shape keeps 4.  The 64 x 64 tile
+  // exists with 4 waves only, whatever its detail string states.
+  p.waves = bm == 256 ? 8 : (env.waves ? env.waves : ((!d.ta && d.tb) ? 4 : 8));
+  // LDS-DMA staging (global_load_lds_dwordx4) whenever the 16-B vector conditions hold
+  p.vec = vec;
+  p.gl = vec && env.glds != 0;
+  const Variant v = with_trans(d.ta, d.tb, [&](auto ta, auto tb) {
+    return f32_variant<decltype(ta)::value, decltype(tb)::value>(bm, p.waves, p.vec, p.gl);
+  });
+  if (int rc = tiles_and_split(kFamF32, v, 32, true, false)) return rc;
+  p.grid = dim3((unsigned)p.ka.nblk, 1, (unsigned)d.batch);
+  p.block = dim3(p.nw * 64);
+  return SRK_OK;
+}
+
+// The launch's kernel and shape as srk_prof_kernels reports them.
+void gemm_plan_detail(const GemmPlan& p, const GemmDesc& d, char (&out)[96]) {
+  const char ta = d.ta ? 'T' : 'N', tb = d.tb ? 'T' : 'N';
+  const long long M = d.M, N = d.N, K = d.K;
+  switch (p.family) {
+    case kFamSkinny:
+      snprintf(out, sizeof(out), "%s_kernel<%c%c> %lldx%lldx%lld",
+               p.skinny == 0 ? "skinny_n" : p.skinny == 1 ? "skinny_m" : "skinny_k", ta, tb, M, N, K);
+      break;
+    case kFamF32:
+      snprintf(out, sizeof(out), "gemm_f32_kernel<%c%c,%dx%d,%dw> %lldx%lldx%lld b%lld s%d", ta, tb, p.bm, p.bn, p.waves, M,
+               N, K, (long long)d.batch, p.splits);
+      break;
+    case kFamLp:
+    case kFamH16:
+      snprintf(out, sizeof(out), "gemm_%s_kernel<%c%c,%dx%d> %lldx%lldx%lld s%d", p.family == kFamLp ? "lp" : "h16", ta, tb,
+               p.bm, p.bn, M, N, K, p.splits);
+      break;
+    case kFamG16:
+    case kFamP32:
+      snprintf(out, sizeof(out), "gemm_%s_kernel<%c%c> %lldx%lldx%lld b%d s%d%s", p.family == kFamG16 ? "g16" : "p32", ta, tb,
+               M, N, K, d.batch, p.splits, p.streamk ? " streamk" : "");
+      break;
+    default: out[0] = 0;
+  }
+}
+
+// Run a plan: scratch (a growth step's device synchronization stays outside the timed scope), kernel arguments,
+// the profiler scope, the kernel, then the stream-K fixup and the split reductions it planned.
+int gemm_launch(const GemmPlan& p, const GemmDesc& d, hipStream_t s) {
+  if (p.family == kFamNone) return SRK_OK;
+  KernelArgs ka = p.ka;
+  ka.d = d;
+  if (const size_t need = p.slab_floats + p.rs_floats + p.sk_floats) {
+    float* scratch = nullptr;
+    if (int rc = g_scratch.get(need, &scratch)) return rc;
+    if (p.slab_floats) ka.partial = scratch;
+    if (p.rs_floats) ka.rs_partial = scratch + p.slab_floats;
+    if (p.sk_floats) ka.sk_slab = scratch + p.slab_floats + p.rs_floats;
+  }
+  ProfScope prof(p.name, s, p.flops);
+  prof.bytes(p.bytes);
+  if (prof.on()) {
+    char detail[96];
+    gemm_plan_detail(p, d, detail);
+    prof.detail("%s", detail);
+  }
+  if (p.family == kFamSkinny) hipLaunchKernelGGL(p.skinny_kernel, p.grid, p.block, 0, s, d);
+  else hipLaunchKernelGGL(p.kernel, p.grid, p.block, 0, s, ka);
+  if (p.streamk) hipLaunchKernelGGL(sk_fixup_kernel, dim3((unsigned)ka.tiles * kSkFixupSlices), dim3(256), 0, s, ka);
+  SRK_CHECK_HIP(hipGetLastError());
+  if (p.reduce) {
+    const int64_t n = d.M * d.N;
+    if (p.reduce == 4)
+      hipLaunchKernelGGL(splitk_reduce4_kernel, dim3((unsigned)((n / 4 + 255) / 256), (unsigned)d.batch), dim3(256), 0,
+                         s, d, ka.partial, p.splits);
+    else
+      hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)d.batch), dim3(256), 0, s, d,
+                         ka.partial, p.splits);
+    if (p.rowsum_reduce)
+      hipLaunchKernelGGL(rowsum_reduce_kernel, dim3((unsigned)((d.M + 255) / 256), (unsigned)d.batch), dim3(256), 0, s,
+                         d.rowsum, d.rowsum_beta, ka.rs_partial, d.M, p.splits, d.sRS);
+    SRK_CHECK_HIP(hipGetLastError());
+  }
+  return SRK_OK;
+}
+
+}  // namespace
+
+bool gemm_f32_batched_rowsum_ok(const GemmDesc& d) {
+  // batched row sums exist only on the fp32-operand ping-pong kernel; a batched launch spans batch - 1
+  // strides past the first operand, and the whole span must stay inside that kernel's 32-bit offsets
+  GemmPlan p;
+  if (gemm_plan(d, p) != SRK_OK || p.family != kFamP32) return false;
+  const double span_a = p.ext_a + (double)(d.batch - 1) * d.sA * 4, span_b = p.ext_b + (double)(d.batch - 1) * d.sB * 4;
+  return span_a < kExtP32 && span_b < kExtP32;
+}
+
+int gemm_f32(const GemmDesc& d, hipStream_t s) {
+  GemmPlan p;
+  if (int rc = gemm_plan(d, p)) return rc;
+  return gemm_launch(p, d, s);
 }
 
 int colsum_f32(const float* X, int64_t M, int64_t N, int64_t ldx, float* out, float beta, hipStream_t s) {
@@ -2063,7 +2091,7 @@ int colsum_f32(const float* X, int64_t M, int64_t N, int64_t ldx, float* out, fl
   } else {
     const int64_t rows_per = (M + rsplit - 1) / rsplit;
     float* part = nullptr;
-    if (int rc = get_scratch((size_t)rsplit * N, &part)) return rc;
+    if (int rc = g_scratch.get((size_t)rsplit * N, &part)) return rc;
     hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)cblocks, (unsigned)rsplit), dim3(256), 0, s, X, M, N, ldx, out,
                        beta, rows_per, part);
     hipLaunchKernelGGL(rowsum_reduce_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, out, beta, part, N,
@@ -2146,15 +2174,37 @@ extern "C" int srk_gemm_16_batched(int trans_a, int trans_b, int64_t M, int64_t 
   SRK_API_END
 }
 
-namespace srk {
-int release_gemm_scratch() {
-  std::lock_guard<std::mutex> lk(g_scratch_mu);
-  SRK_CHECK_HIP(hipDeviceSynchronize());
-  for (Scratch& s : g_scratch) {
-    if (s.p) SRK_CHECK_HIP(hipFree(s.p));
-    s = Scratch{};
+// The plan gemm_f32 would run for these arguments, as text (tests/test_gemm_plan.py; no GPU needed): only
+// gemm_plan runs, the addresses are inspected for alignment and never dereferenced.
+extern "C" int srk_gemm_plan_describe(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, int64_t lda,
+                                      int64_t ldb, int64_t ldc, int batch, int64_t sA, int64_t sB, int64_t sC,
+                                      int bias_mode, int has_rowsum, int operands16, int prec, int no_split,
+                                      int plan_batch, uint64_t a_addr, uint64_t b_addr, uint64_t c_addr,
+                                      uint64_t bias_addr, char* buf, int64_t cap) {
+  SRK_API_BEGIN
+  SRK_REQUIRE(buf && cap > 0, SRK_ERR_INVALID, "gemm_plan_describe: no buffer");
+  buf[0] = 0;
+  srk::GemmDesc d;
+  d.M = M; d.N = N; d.K = K;
+  d.lda = lda; d.ta = trans_a != 0;
+  d.ldb = ldb; d.tb = trans_b != 0;
+  if (operands16) {
+    d.A16 = reinterpret_cast<const uint16_t*>(a_addr); d.B16 = reinterpret_cast<const uint16_t*>(b_addr);
+  } else {
+    d.A = reinterpret_cast<const float*>(a_addr); d.B = reinterpret_cast<const float*>(b_addr);
   }
-  g_scratch_gen.fetch_add(1);
+  d.C = reinterpret_cast<float*>(c_addr); d.ldc = ldc;
+  d.bias = reinterpret_cast<const float*>(bias_addr); d.bias_mode = bias_mode;
+  d.batch = batch; d.sA = sA; d.sB = sB; d.sC = sC;
+  if (has_rowsum) d.rowsum = reinterpret_cast<float*>(uintptr_t(16));
+  d.prec = prec; d.no_split = no_split != 0; d.plan_batch = plan_batch;
+  srk::GemmPlan p;
+  if (int rc = srk::gemm_plan(d, p)) return rc;
+  char detail[96];
+  srk::gemm_plan_detail(p, d, detail);
+  snprintf(buf, (size_t)cap, "%s|%s\nreduce=%s%s scratch=%zu", p.family == srk::kFamNone ? "none" : p.name, detail,
+           p.reduce == 4 ? "splitk_reduce4" : p.reduce ? "splitk_reduce" : "none", p.rowsum_reduce ? "+rowsum" : "",
+           p.slab_floats + p.rs_floats + p.sk_floats);
   return SRK_OK;
+  SRK_API_END
 }
-}  // namespace srk

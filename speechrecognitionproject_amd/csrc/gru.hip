@@ -23,7 +23,6 @@
 //   words | the in4 pad block (in % 4 != 0) | the 16-bit block (H = 512: x16, W16, y16 / bias partials, dW_ih
 //   and dx at width in8); srk_gru_top_last_bwd appends its [B][T][2H] dy.
 #include <algorithm>
-#include <mutex>
 
 #include "gemm.h"
 #include "gru_internal.h"
@@ -504,30 +503,7 @@ __global__ void dwhh_dbias_reduce_kernel(const float* __restrict__ part, int npa
 }
 
 // grow-only scratch of the fused backward's dW_hh partials (graph-safe: bumps g_scratch_gen on growth)
-struct GruScratch {
-  float* p = nullptr;
-  size_t floats = 0;
-};
-GruScratch g_gs[64];
-std::mutex g_gs_mu;
-
-int gru_scratch(size_t floats, float** out) {
-  int dev = 0;
-  SRK_CHECK_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_gs_mu);
-  GruScratch& sc = g_gs[dev & 63];
-  if (sc.floats < floats) {
-    if (sc.p) {
-      SRK_CHECK_HIP(hipDeviceSynchronize());
-      SRK_CHECK_HIP(hipFree(sc.p));
-    }
-    sc.floats = floats + floats / 4;
-    SRK_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&sc.p), sc.floats * sizeof(float)));
-    g_scratch_gen.fetch_add(1);
-  }
-  *out = sc.p;
-  return SRK_OK;
-}
+ScratchPool g_gs;
 
 inline int64_t pad4(int64_t v) { return (v + 3) / 4 * 4; }
 inline bool padded_in(int64_t in) { return in % 4 != 0; }
@@ -536,18 +512,6 @@ int pad_cols(const float* src, int64_t rows, int64_t cols, float* dst, hipStream
 }
 
 }  // namespace
-
-int release_gru_scratch() {
-  std::lock_guard<std::mutex> lk(g_gs_mu);
-  SRK_CHECK_HIP(hipDeviceSynchronize());
-  for (GruScratch& sc : g_gs) {
-    if (sc.p) SRK_CHECK_HIP(hipFree(sc.p));
-    sc.p = nullptr;
-    sc.floats = 0;
-  }
-  g_scratch_gen.fetch_add(1);
-  return SRK_OK;
-}
 }  // namespace srk
 
 using srk::GemmDesc;
@@ -878,7 +842,7 @@ static int layer_bwd(const float* x, const void* x16_in, int64_t B, int64_t T, i
     if (h16) {   // the kernel writes dgi16 / dgh16 and the bias-gradient partials
       p.dgi16 = const_cast<uint16_t*>(m_dgi.h); p.dgh16 = const_cast<uint16_t*>(m_dgh.h); p.dbias = ws + L.part;
       if (dw_parts) {
-        if ((rc = srk::gru_scratch((size_t)dw_parts * 2 * 3 * H * H, &p.dw_part))) return rc;
+        if ((rc = srk::g_gs.get((size_t)dw_parts * 2 * 3 * H * H, &p.dw_part))) return rc;
         p.y16_in = m_y.h;
       }
     } else {

@@ -59,6 +59,44 @@ int g_opt_gemm_skinny = 1;
 int g_opt_attn_pool_regs = 1;
 std::atomic<int64_t> g_scratch_gen{0};
 
+ScratchPool* ScratchPool::head_ = nullptr;
+
+int ScratchPool::get(size_t floats, float** out) {
+  int dev = 0;
+  SRK_CHECK_HIP(hipGetDevice(&dev));
+  SRK_REQUIRE(dev >= 0 && dev < 64, SRK_ERR_INVALID, "device out of range");
+  std::lock_guard<std::mutex> lk(mu_);
+  Slot& s = slots_[dev];
+  if (s.floats < floats) {   // grow-only: steady state never allocates
+    if (float* old = s.p) {
+      SRK_CHECK_HIP(hipDeviceSynchronize());
+      s = Slot{};
+      SRK_CHECK_HIP(hipFree(old));
+    }
+    const size_t want = floats + floats / 4;
+    float* p = nullptr;
+    SRK_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&p), want * sizeof(float)));
+    s = Slot{p, want};
+    g_scratch_gen.fetch_add(1);
+  }
+  *out = s.p;
+  return SRK_OK;
+}
+
+int ScratchPool::release_all() {
+  SRK_CHECK_HIP(hipDeviceSynchronize());
+  for (ScratchPool* pool = head_; pool; pool = pool->next_) {
+    std::lock_guard<std::mutex> lk(pool->mu_);
+    for (Slot& s : pool->slots_) {
+      float* old = s.p;
+      s = Slot{};
+      if (old) SRK_CHECK_HIP(hipFree(old));
+    }
+  }
+  g_scratch_gen.fetch_add(1);
+  return SRK_OK;
+}
+
 static thread_local std::string g_last_error;
 
 void set_error(const char* fmt, ...) {
@@ -371,10 +409,7 @@ int srk_set_option(const char* name, int64_t value) {
   SRK_REQUIRE(name, SRK_ERR_INVALID, "set_option: null name");
   const std::string n(name);
   if (n == "release_scratch") {   // free the library's grow-only scratch buffers (invalidates captured graphs)
-    if (int rc = srk::release_gemm_scratch()) return rc;
-    if (int rc = srk::release_conv_scratch()) return rc;
-    if (int rc = srk::release_gru_scratch()) return rc;
-    return srk::release_bn_scratch();
+    return srk::ScratchPool::release_all();
   }
   if (n == "gru_persistent") {
     srk::g_opt_gru_persistent = value != 0;

@@ -4,6 +4,7 @@
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
+#include <mutex>
 #include <string>
 
 #include "../../include/srk.h"
@@ -103,11 +104,29 @@ extern int g_opt_conv_fwd_fp32;
 // Bumped whenever a library scratch buffer is (re)allocated: a captured HIP graph that refers to the
 // old buffer must not be replayed (srk_scratch_generation; graphs.GraphedStep checks it).
 extern std::atomic<int64_t> g_scratch_gen;
-// Free every grow-only scratch buffer of one pool (device-synchronizing; bumps g_scratch_gen).
-int release_gemm_scratch();
-int release_conv_scratch();
-int release_bn_scratch();
-int release_gru_scratch();
+// Grow-only library scratch: one buffer per device, handed out again until a larger one is asked for.  Every
+// use declares its own instance (runtime.hip); srk_set_option("release_scratch") frees them all.
+class ScratchPool {
+ public:
+  ScratchPool() : next_(head_) { head_ = this; }
+  ScratchPool(const ScratchPool&) = delete;
+  ScratchPool& operator=(const ScratchPool&) = delete;
+  // *out = at least `floats` floats on the current device.  Growing synchronizes the device, frees the old buffer
+  // and bumps g_scratch_gen; a failed allocation leaves the device's slot empty.
+  int get(size_t floats, float** out);
+  // Free every buffer of every instance (device-synchronizing; bumps g_scratch_gen).
+  static int release_all();
+
+ private:
+  struct Slot {
+    float* p = nullptr;
+    size_t floats = 0;
+  };
+  Slot slots_[64];   // by device index
+  std::mutex mu_;
+  ScratchPool* next_;           // the instances, linked as they are constructed
+  static ScratchPool* head_;
+};
 extern int g_opt_gemm16_kernel;
 // Kernel of the fp32 GEMM (srk_set_option "gemm32_kernel"): 0 = by shape, 1 = register-staged
 // gemm_f32_kernel, 2 = LDS-DMA ping-pong gemm_p32_kernel.
@@ -188,6 +207,8 @@ class ProfScope {
   // The launch's ALGORITHMIC HBM bytes (matrix kernels, whose `work` is flops): each operand tensor read
   // once + the output written once — what PMC traffic is priced against.
   void bytes(double b) { bytes_ = b; }
+  // Whether this scope records (profiling on): callers skip building a detail string otherwise.
+  bool on() const { return a_ != nullptr; }
 
  private:
   const char* name_;

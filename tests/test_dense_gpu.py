@@ -474,3 +474,78 @@ def test_gemm_streamk(gpu, M, N, K, ta, beta, bias):
     tol = 1e-5 * (1 + (A.abs().max() * B.abs().max() * K).item())
     assert (outs[0] - ref).abs().max() <= tol
     assert (outs[0] - outs[1]).abs().max() <= tol
+
+
+@pytest.mark.parametrize("entry,opts,prec,ta,tb,M,N,K,off,beta,bias", [
+    ("f32", {}, "fp32", 0, 1, 256, 12, 1024, 0, 0.0, 1),              # skinny_n
+    ("f32", {}, "bf16", 1, 0, 12, 260, 300, 0, 1.5, 0),               # skinny_m
+    ("f32", {}, "fp16", 0, 0, 300, 260, 16, 0, 0.0, 2),               # skinny_k
+    ("f32", {"gemm_skinny": 0}, "fp32", 0, 0, 300, 12, 1024, 0, 0.0, 0),   # the tile path instead
+    ("f32", {}, "fp32", 0, 0, 300, 260, 1024, 0, 1.5, 1),             # 64 x 64, split K, vector reduce
+    ("f32", {}, "fp32", 0, 1, 300, 260, 1024, 0, 0.0, 0),             # x W^T: 4 waves
+    ("f32", {}, "fp32", 1, 0, 300, 259, 1023, 0, 0.0, 2),             # scalar staging, scalar reduce
+    ("f32", {}, "fp32", 1, 1, 37, 29, 39, 1, 0.0, 0),                 # operand one element off 16 B
+    ("f32", {}, "fp32", 0, 0, 65, 65, 17, 0, 0.0, 0),                 # unsplit
+    ("rowsum", {}, "fp32", 1, 0, 96, 64, 1024, 0, 1.5, 0),            # split K with row-sum partials
+    ("f32", {"gemm32_kernel": 2}, "fp32", 0, 0, 300, 260, 1024, 0, 0.0, 1),   # ping-pong, split
+    ("f32", {"gemm32_kernel": 2}, "fp32", 1, 1, 256, 256, 64, 0, 1.5, 0),
+    ("rowsum", {"gemm32_kernel": 2}, "fp32", 1, 0, 300, 260, 1024, 0, 0.0, 0),
+    ("f32", {"gemm32_kernel": 2}, "fp32", 0, 0, 300, 260, 1024, 1, 0.0, 0),   # ... refused by alignment: tile kernel
+    ("f32", {}, "bf16", 0, 0, 300, 260, 1024, 0, 0.0, 1),             # gemm_lp_kernel, vector staging
+    ("f32", {}, "fp16", 0, 1, 299, 260, 1023, 0, 1.5, 2),             # gemm_lp_kernel, scalar staging
+    ("rowsum", {}, "bf16", 1, 0, 300, 260, 1024, 0, 0.0, 0),
+    ("g16", {}, "bf16", 0, 0, 296, 256, 1024, 0, 0.0, 1),             # gemm_h16_kernel
+    ("g16", {}, "fp16", 1, 0, 296, 256, 1024, 0, 1.5, 0),
+    ("g16", {"gemm16_kernel": 2}, "bf16", 0, 1, 296, 256, 1024, 0, 0.0, 2),   # gemm_g16_kernel
+    ("g16b", {}, "fp16", 0, 0, 296, 256, 1024, 0, 0.0, 0),            # batched: gemm_g16_kernel
+])
+def test_gemm_runs_what_the_plan_describes(gpu, entry, opts, prec, ta, tb, M, N, K, off, beta, bias):
+    """What srk_gemm_plan_describe names for a call's arguments is the one (name, detail) record the call leaves in
+    srk_prof_kernels: every kernel family reachable below 300 x 260 x 1024 through the options."""
+    import ctypes
+    from speechrecognitionproject_amd import _lib
+    o16, batch = entry in ("g16", "g16b"), 2 if entry == "g16b" else 1
+    ar, ac = (K, M) if ta else (M, K)
+    br, bc = (N, K) if tb else (K, N)
+    g = torch.Generator().manual_seed(M + N + K)
+    dt = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(prec) if o16 else torch.float32
+    A = torch.randn(batch * ar * ac + 8, generator=g).to(dt).cuda()[off:]
+    B = torch.randn(batch * br * bc + 8, generator=g).to(dt).cuda()
+    C = torch.zeros(batch, M, N, device="cuda")
+    bv = torch.randn(max(M, N), generator=g).cuda()
+    rs = torch.zeros(M, device="cuda")
+    sA, sB, sC = (ar * ac, br * bc, M * N) if batch > 1 else (0, 0, 0)
+    buf = ctypes.create_string_buffer(512)
+    try:
+        _lib.set_matmul_precision(prec)
+        for k, v in opts.items():
+            _lib.set_option(k, v)
+        call("srk_gemm_plan_describe", ta, tb, M, N, K, ac, bc, N, batch, sA, sB, sC, bias, int(entry == "rowsum"),
+             int(o16), -1, 0, 0, A.data_ptr(), B.data_ptr(), C.data_ptr(), bv.data_ptr() if bias else 0, buf, len(buf))
+        _lib.prof_enable(1)
+        if entry == "rowsum":
+            call("srk_gemm_rowsum_f32", ta, tb, M, N, K, 0.5, ptr(A), ac, ptr(B), bc, beta, ptr(C), N, ptr(rs), stream_ptr())
+        elif entry == "g16b":
+            call("srk_gemm_16_batched", ta, tb, M, N, K, 0.5, ptr(A), ac, sA, ptr(B), bc, sB, beta, ptr(C), N, sC, batch,
+                 stream_ptr())
+        else:
+            call("srk_gemm_16" if o16 else "srk_gemm_f32", ta, tb, M, N, K, 0.5, ptr(A), ac, ptr(B), bc, beta, ptr(C), N,
+                 ptr(bv) if bias else None, bias, stream_ptr())
+        torch.cuda.synchronize()
+        ran = [(k["name"], k["kernel"], k["launches"]) for k in _lib.prof_kernels()]
+    finally:
+        _lib.prof_enable(0)
+        for k in opts:
+            _lib.set_option(k, 1 if k == "gemm_skinny" else 0)
+        _lib.set_matmul_precision("fp32")
+    name, detail = buf.value.decode().split("\n")[0].split("|")
+    assert ran == [(name, detail, 1)]
+    # and the result is the product: fp32 accumulation over K terms (K 2^-23 of sum |a| |b|), plus in 16-bit modes
+    # both operands rounded to at worst bf16 (2^-8 each)
+    opA, opB = A[:ar * ac].view(ar, ac).float().cpu().double(), B[:br * bc].view(br, bc).float().cpu().double()
+    opA, opB = (opA.T if ta else opA), (opB.T if tb else opB)
+    ref = 0.5 * (opA @ opB)
+    if bias:
+        ref += bv[:N].cpu().double() if bias == 1 else bv[:M].cpu().double()[:, None]
+    eps = K * 2.0 ** -23 + (2.0 ** -7 if prec != "fp32" else 0.0)
+    assert (C[0].cpu().double() - ref).abs().max() <= eps * 0.5 * (opA.abs() @ opB.abs()).max() + 1e-6

@@ -1,0 +1,79 @@
+"""The GEMM launch plan, read without a GPU (srk_gemm_plan_describe runs csrc/gemm.hip's gemm_plan and nothing else).
+
+gemm_plan_table.json holds descriptors from every kernel family, tile configuration and rule boundary of the dispatch
+(one stream-K row, batched rows, the GRU's internal no_split / plan_batch descriptors) with the (name, detail) record
+the PARENT of the plan refactor gave them: srk_prof_kernels on the MI355X for the launches, srk_last_error for the
+rejected arguments ("recorded" in each row says which).  The plan must name exactly those."""
+import ctypes
+import json
+import os
+
+import pytest
+
+from speechrecognitionproject_amd import _lib
+
+TABLE = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "gemm_plan_table.json")))
+BATCHED_ROWSUM_ERROR = "gemm: batched row sums need the fp32 ping-pong kernel (16-B operand rows)"
+
+
+def describe(a):
+    """("name|detail", None) or (None, error message) for one table row's arguments."""
+    buf = ctypes.create_string_buffer(512)
+    base = 1 << 20   # addresses are read for alignment and nullness only
+    try:
+        _lib.call("srk_gemm_plan_describe", a["ta"], a["tb"], a["M"], a["N"], a["K"], a["lda"], a["ldb"], a["ldc"],
+                  a["batch"], a["sA"], a["sB"], a["sC"], a["bias_mode"], a["rowsum"], a["ops16"], a["prec"],
+                  a["no_split"], a["plan_batch"], base + a["a_mod16"], 2 * base + a["b_mod16"],
+                  0 if a["c_null"] else 3 * base, 4 * base if a["bias"] else 0, buf, len(buf))
+    except _lib.SrkError as e:
+        return None, str(e).split("): ", 1)[1]
+    return buf.value.decode().split("\n")[0], None
+
+
+@pytest.mark.parametrize("row", TABLE, ids=[r["case"] for r in TABLE])
+def test_plan_names_what_the_parent_launched(row):
+    try:
+        for k, v in row["options"].items():
+            _lib.set_option(k, v)
+        got, err = describe(row["args"])
+    finally:
+        for k in row["options"]:
+            _lib.set_option(k, {"gemm_skinny": 1, "gemm_streamk": 1}.get(k, 0))
+    assert got == row.get("expect")
+    assert err == row.get("error")
+
+
+def test_table_covers_the_dispatch():
+    """Every kernel family, every tile configuration, stream-K, a batched launch, every argument error of the plan."""
+    seen = " ".join(r.get("expect", "") for r in TABLE)
+    for k in ("skinny_n_kernel", "skinny_m_kernel", "skinny_k_kernel", "gemm_f32_kernel<NN,64x64,8w>", ",128x128,8w>",
+              ",128x128,4w>", ",256x128,8w>", "gemm_lp_kernel<NN,128x128>", "gemm_lp_kernel<NN,256x128>",
+              "gemm_h16_kernel<NN,128x128>", "gemm_h16_kernel<NN,256x128>", "gemm_h16_kernel<NT,256x256>",
+              "gemm_g16_kernel", "gemm_p32_kernel", " streamk", " b2 "):
+        assert k in seen, k
+    assert len({r["error"] for r in TABLE if "error" in r}) == 10
+
+
+@pytest.mark.parametrize("ta,tb", [(0, 0), (0, 1), (1, 0), (1, 1)])
+@pytest.mark.parametrize("align", ["aligned", "a+4", "b+4", "lda+1", "ldb+2", "sA+2", "K+1"])
+@pytest.mark.parametrize("kernel32", [0, 1, 2])
+def test_batched_row_sums_run_on_the_ping_pong_kernel_or_are_refused(ta, tb, align, kernel32):
+    """gemm_f32_batched_rowsum_ok asks the plan: a batch-2 launch with row sums is either refused with the batched
+    row-sum error or planned on gemm_p32_kernel, never anything else.  The same descriptor at batch 1 (planned as 2:
+    what the BiGRU launches per direction) cannot be refused; it is on gemm_p32_kernel exactly when the batch-2 plan
+    is, so both questions have one answer."""
+    M, N, K = 1536, 512, 1284 + (align == "K+1")
+    ar, ac = (K, M) if ta else (M, K)
+    br, bc = (N, K) if tb else (K, N)
+    a = dict(ta=ta, tb=tb, M=M, N=N, K=K, lda=ac + (align == "lda+1"), ldb=bc + 2 * (align == "ldb+2"), ldc=N, batch=2,
+             sA=ar * (ac + 1) + 2 * (align == "sA+2"), sB=br * (bc + 2), sC=M * N, bias_mode=0, rowsum=1, ops16=0, prec=0,
+             no_split=0, plan_batch=0, a_mod16=4 * (align == "a+4"), b_mod16=4 * (align == "b+4"), c_null=0, bias=0)
+    try:
+        _lib.set_option("gemm32_kernel", kernel32)
+        got2, err2 = describe(a)
+        got1, err1 = describe(dict(a, batch=1, plan_batch=2))
+    finally:
+        _lib.set_option("gemm32_kernel", 0)
+    assert (err2 == BATCHED_ROWSUM_ERROR) != (got2 is not None and "|gemm_p32_kernel<" in got2), (got2, err2)
+    assert err1 is None
+    assert ("|gemm_p32_kernel<" in got1) == (got2 is not None), (got1, got2, err2)
