@@ -58,24 +58,27 @@ int srk_prof_read(const char* name, int64_t* count, double* total_ms, double* to
  * bytes where the launch site states them (matrix kernels: operands once + the output; 0 elsewhere).
  * bench.py names the largest single kernel with it and prices PMC traffic against the bytes. */
 int srk_prof_kernels(char* buf, int64_t cap, int64_t* needed);
-/* Runtime options: "gru_persistent" (default 1) = run each GRU layer's recurrence as ONE
- * persistent launch with W_hh resident in LDS (0 = one launch per time step);
- * "matmul_precision" (default 0) = operand precision of the matrix-core kernels (GEMM, GRU
- * recurrence): 0 fp32 (exact, the reference's arithmetic), 1 bf16, 2 fp16 — operands rounded to
- * nearest-even on chip, fp32 accumulation, fp32 tensors in and out (BASELINE.json cfg2 / cfg5);
- * "gemm16_kernel" (default 0 = by shape) = the 16-bit-operand GEMM kernel: 1 register-staged,
- * 2 LDS-DMA ping-pong (same results up to fp32 summation order; for A/B measurements and tests);
- * "gemm32_kernel" (default 0 = by shape) = the same choice for the fp32 GEMM;
- * "conv16_sources" (default 1) = bf16 / fp16 convolutions gather from one pre-rounded 16-bit copy
- * of their operands (0 = round at LDS-store time; bit-identical results either way);
- * "conv_ring" (default 0x77) = the LDS-DMA ring implicit-GEMM convolutions where the shape
- * qualifies (bits 0-2 fp32 fwd / dgrad / wgrad, 4-6 the same in 16 bit, 7 also the pooled forward
- * and the fp32 forward at K < 3072); "conv_unpool16" (default 1) = the 16-bit pooled-conv backward
- * writes the dense dY straight as its 16-bit operand copy; "gru_dwhh_fused" (default 1) = the 16-bit
- * BiGRU backward accumulates dW_hh inside the recurrence kernel (0 = a GEMM over dgh16 / y16; bits
- * 1 / 2 of a non-zero value: timing variants, bitwise bit 0's results) — results equal up to fp32
- * summation order (A/B measurements and tests). */
+/* Runtime options.  Every option has a public name, a default and a rule for the values it accepts: a
+ * boolean (any value, stored as value != 0), a range lo..hi, an explicit set such as 128|256, or, for
+ * "release_scratch", an action that stores nothing.  srk_set_option refuses (SRK_ERR_INVALID, state
+ * unchanged) an unknown name or a value outside the rule; srk_option_list is the full list with each
+ * option's default, current value, rule and one-line description (csrc/options.h is its source).
+ * Two an integrator meets: "matmul_precision" (default 0) = operand precision of the matrix-core
+ * kernels (GEMM, GRU recurrence): 0 fp32 (exact, the reference's arithmetic), 1 bf16, 2 fp16 — operands
+ * rounded to nearest-even on chip, fp32 accumulation, fp32 tensors in and out (BASELINE.json cfg2 / cfg5);
+ * "conv_ring" (default 0x77) = the LDS-DMA ring implicit-GEMM convolutions where the shape qualifies
+ * (bits 0-2 fp32 fwd / dgrad / wgrad, 4-6 the same in 16 bit, 7 also the pooled forward and the fp32
+ * forward at K < 3072) — results equal up to fp32 summation order (A/B measurements and tests). */
 int srk_set_option(const char* name, int64_t value);
+/* *value = the value for which srk_set_option(name, *value) reproduces the option's current state (so
+ * "gru_dc_offset_ns" in ns, "gru_dwhh_fused" as normalised).  SRK_ERR_INVALID for an unknown name, a null
+ * pointer or the action "release_scratch". */
+int srk_get_option(const char* name, int64_t* value);
+/* One "name\tdefault\tcurrent\taccepts\tdoc\n" line per option, in the order of csrc/options.h, into buf
+ * with the convention of srk_prof_kernels (NUL-terminated, truncated at cap bytes, *needed = the full
+ * size).  accepts is "bool", "lo..hi", "a|b", "pointer" or "action"; an action's default and current
+ * columns say "action". */
+int srk_option_list(char* buf, int64_t cap, int64_t* needed);
 /* Number of bounded spin-waits of the persistent kernels that gave up (synchronizes the
  * device; must stay 0 — a non-zero value means a co-residency assumption failed).  -1 on error. */
 int64_t srk_spin_timeouts(void);

@@ -4,6 +4,7 @@ or a GPU is missing, every op raises.
 torch is imported first on purpose: its bundled libamdhip64.so.7 is then the HIP runtime that
 libsrk.so binds to (same SONAME), so torch tensors, streams and our kernels share one runtime.
 """
+import contextlib
 import ctypes
 import os
 import re
@@ -34,6 +35,8 @@ _SIGS = {
     "srk_diag_acc_store": [_P, _I64, _I, _P],
     "srk_diag_tr16_read": [_P, _I64, _P, _P],
     "srk_set_option": [ctypes.c_char_p, _I64],
+    "srk_get_option": [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)],
+    "srk_option_list": [ctypes.c_char_p, _I64, ctypes.POINTER(ctypes.c_int64)],
     "srk_spin_timeouts": [],
     "srk_scratch_generation": [],
     "srk_gru_audit_words": [_I64, _I, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
@@ -167,11 +170,10 @@ def lib():
         if v != ABI_VERSION:
             raise SrkError("libsrk.so ABI version %d != expected %d (rebuild)" % (v, ABI_VERSION))
         _lib = L
-        # A/B measurements: SRK_OPTIONS="conv_tile=256,gru_lp2=0" applies srk_set_option at load
+        # A/B measurements: SRK_OPTIONS="conv_tile=256,gru_lp_32x32=0" applies set_option at load
         for item in filter(None, os.environ.get("SRK_OPTIONS", "").split(",")):
             name, _, val = item.partition("=")
-            call("srk_set_option", name.strip().encode(), int(val))
-            _options[name.strip()] = int(val)
+            set_option(name.strip(), int(val))
     return _lib
 
 
@@ -223,23 +225,55 @@ def scratch_generation():
     return int(lib().srk_scratch_generation())
 
 
-_options = {}
+PRECISIONS = {"fp32": 0, "bf16": 1, "fp16": 2}
+_precision = "fp32"   # mirror of the library's "matmul_precision": nn.py reads it on every forward
 
 
 def set_option(name, value):
     """srk_set_option (include/srk.h): e.g. set_option("gru_persistent", 0)."""
+    global _precision
     call("srk_set_option", name.encode(), int(value))
-    _options[name] = int(value)
+    if name == "matmul_precision":
+        _precision = next(k for k, v in PRECISIONS.items() if v == int(value))
 
 
-def option(name, default=0):
-    """The last value this process gave option `name` (set_option / SRK_OPTIONS), else `default`."""
-    lib()
-    return _options.get(name, default)
+def option(name, default=None):
+    """srk_get_option: the library's current value of option `name` (`default` is ignored)."""
+    v = ctypes.c_int64(0)
+    call("srk_get_option", name.encode(), ctypes.byref(v))
+    return int(v.value)
 
 
-PRECISIONS = {"fp32": 0, "bf16": 1, "fp16": 2}
-_precision = "fp32"
+@contextlib.contextmanager
+def options(**values):
+    """Run a block with the given options set; on exit, also by an exception, every one is put back to the
+    value it had on entry (not to its default).  If a value is refused, those already set are put back first."""
+    saved = []
+    try:
+        for name, value in values.items():
+            old = option(name)
+            set_option(name, value)
+            saved.append((name, old))
+        yield
+    finally:
+        for name, old in reversed(saved):
+            set_option(name, old)
+
+
+def option_table():
+    """srk_option_list: {name: {"default", "current", "accepts", "doc"}} in the library's order; default and
+    current are ints, or None for an action ("release_scratch")."""
+    need = ctypes.c_int64(0)
+    call("srk_option_list", None, 0, ctypes.byref(need))
+    buf = ctypes.create_string_buffer(int(need.value))
+    call("srk_option_list", buf, len(buf), ctypes.byref(need))
+    out = {}
+    for line in buf.value.decode().splitlines():
+        name, default, current, accepts, doc = line.split("\t")
+        action = accepts == "action"
+        out[name] = {"default": None if action else int(default), "current": None if action else int(current),
+                     "accepts": accepts, "doc": doc}
+    return out
 
 
 def set_matmul_precision(name):

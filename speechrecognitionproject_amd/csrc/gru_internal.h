@@ -130,23 +130,6 @@ GruRecPlan gru_rec_plan(int64_t B, int64_t T, int64_t H, int in_fused, int prec,
 // Enqueue the whole recurrence (all T steps; batch split into the plan's co-resident chunks).
 int gru_persistent_launch(GruPArgs a, const GruRecPlan& plan, bool backward, hipStream_t s);
 
-// Runtime options (srk_set_option): persistent GRU recurrence on/off (default on).
-extern int g_opt_gru_persistent;
-extern unsigned long long* g_opt_gru_trace;   // device buffer or nullptr
-extern unsigned g_opt_gru_spin_limit;          // 0 = default (~2 s); test hook "gru_spin_limit"
-extern int g_opt_gru_xcd_local;                // XCD-local hand-off when the census allows (default 1)
-extern int g_opt_gru_lp_wide;                 // 16-bit recurrence over > 256 rows: 64-row workgroups, one launch (default 1)
-extern int g_opt_gru_lp2;                      // 16-bit recurrence on 32 x 32 workgroups (default 1)
-extern int g_opt_gru_dc;                       // fp32 recurrence: two independent row chains per workgroup (default 1)
-extern unsigned g_opt_gru_dc_offset;            // chain-1 start delay (ticks of 10 ns), default 200 (2 us)
-extern int g_opt_gru_fast_cell;                 // fp32 two-chain forward: hardware exp / rcp cell math (default 1)
-extern int g_opt_gru_dc_prio;                   // fp32 two-chain kernels: static priority of one chain (0, 1, 2)
-extern int g_opt_gru_dwhh_fused;             // fused recurrent weight gradient in the 16-bit backward (default 1)
-extern int g_opt_gru_fwd_worker;               // 16-bit forward: output / input worker waves (default 0 until measured)
-// Last-step top layer (srk_gru_top_last_*, fp32 persistent path): 0 = the full layer, 1 = the backward GEMMs
-// without their all-zero reverse-direction parts, 2 = also the reverse direction as its one live cell, 3 = that cell
-// and the forward-only launches of 2 with the full dW_ih / dx GEMMs, bit for bit the full layer's results (default)
-extern int g_opt_gru_top_last;
 // Host-pinned health word (device-mapped pointer in *dev): non-zero once any persistent-kernel
 // spin-wait has given up; read without a device synchronization by srk_health_check.
 int health_word(unsigned** host, unsigned** dev);

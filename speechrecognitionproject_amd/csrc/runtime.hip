@@ -11,6 +11,7 @@
 #include <functional>
 #include <cmath>
 #include <cstdarg>
+#include <cstring>
 #include <mutex>
 #include <vector>
 
@@ -19,44 +20,18 @@
 
 namespace srk {
 
-int g_opt_gru_persistent = 1;
-int g_opt_gemm16_kernel = 0;
-int g_opt_conv16_sources = 1;
-int g_opt_conv_fused_db = 1;
-int g_opt_conv_unpool_gather = 1;
-int g_opt_conv_tile = 128;
-int g_opt_conv_ring = 0x77;
-int g_opt_conv_unpool16 = 1;
-int g_opt_conv_colsum16 = 1;
-int g_opt_conv_ring_qs = 6;
-int g_opt_conv_fast16 = 1;
-int g_opt_conv_row16 = 1;
-int g_opt_conv_row32 = 1;
-int g_opt_conv_fw_gemm = 1;
-int g_opt_conv_row16_dgrad = 2;
-int g_opt_bn_tree = 0;
-int g_opt_mfcc_variant = 3;
-int g_opt_gemm_streamk = 1;
-int g_opt_gemm32_kernel = 0;
+// The plain options' variables with their defaults (options.h), then what the hooked ones store.
+#define SRK_DEFINE_OPTION(type, var, name, accepts, def, doc) type var = def;
+#define SRK_HOOKED_OPTION(name, hook, accepts, def, doc)
+SRK_OPTION_LIST(SRK_DEFINE_OPTION, SRK_HOOKED_OPTION)
+#undef SRK_DEFINE_OPTION
+#undef SRK_HOOKED_OPTION
 static std::atomic<int> g_opt_matmul_prec{kPrecF32};
 thread_local int t_prec_override = -1;
 int matmul_prec() { return t_prec_override >= 0 ? t_prec_override : g_opt_matmul_prec.load(std::memory_order_relaxed); }
-int g_opt_conv_fwd_fp32 = 0;
 unsigned long long* g_opt_gru_trace = nullptr;
-unsigned g_opt_gru_spin_limit = 0;
-int g_opt_gru_xcd_local = 1;
-int g_opt_gru_lp2 = 1;
-int g_opt_gru_lp_wide = 1;
-int g_opt_gru_dc = 1;
 unsigned g_opt_gru_dc_offset = 200;
-int g_opt_gru_fast_cell = 1;
-int g_opt_gru_dc_prio = 0;
 int g_opt_gru_dwhh_fused = 1;
-int g_opt_gru_fwd_worker = 0;
-int g_opt_gru_dwhh_batched = 1;
-int g_opt_gru_top_last = 3;
-int g_opt_gemm_skinny = 1;
-int g_opt_attn_pool_regs = 1;
 std::atomic<int64_t> g_scratch_gen{0};
 
 ScratchPool* ScratchPool::head_ = nullptr;
@@ -384,6 +359,83 @@ int get_tables(const DeviceTables** out) {
   return SRK_OK;
 }
 
+// ---------------------------------------------------------------- runtime options: the table of options.h
+namespace {
+
+// The hooked options: option_set_<hook> stores an accepted value, option_get_<hook> returns the value that sets
+// the current state again.
+int option_set_matmul_precision(int64_t v) { g_opt_matmul_prec.store((int)v); return SRK_OK; }
+int64_t option_get_matmul_precision() { return g_opt_matmul_prec.load(); }
+int option_set_gru_trace_ptr(int64_t v) { g_opt_gru_trace = reinterpret_cast<unsigned long long*>(v); return SRK_OK; }
+int64_t option_get_gru_trace_ptr() { return reinterpret_cast<int64_t>(g_opt_gru_trace); }
+int option_set_gru_dc_offset_ns(int64_t v) { g_opt_gru_dc_offset = (unsigned)(v / 10); return SRK_OK; }
+int64_t option_get_gru_dc_offset_ns() { return (int64_t)g_opt_gru_dc_offset * 10; }
+int option_set_gru_dwhh_fused(int64_t v) { g_opt_gru_dwhh_fused = (v & 1) ? (int)v : 0; return SRK_OK; }
+int64_t option_get_gru_dwhh_fused() { return g_opt_gru_dwhh_fused; }
+int option_set_release_scratch(int64_t) { return ScratchPool::release_all(); }
+constexpr int64_t (*option_get_release_scratch)() = nullptr;
+
+struct Accepts {
+  enum Kind { kBool, kRange, kOneOf, kPointer, kAction } kind;
+  int64_t lo, hi;        // kRange
+  int64_t set[4]; int n;   // kOneOf
+  bool ok(int64_t v) const {
+    if (kind == kRange) return v >= lo && v <= hi;
+    if (kind != kOneOf) return true;
+    for (int i = 0; i < n; ++i)
+      if (set[i] == v) return true;
+    return false;
+  }
+  std::string text() const {
+    std::string s;
+    switch (kind) {
+      case kBool: return "bool";
+      case kRange: return std::to_string(lo) + ".." + std::to_string(hi);
+      case kOneOf:
+        for (int i = 0; i < n; ++i) s += (i ? "|" : "") + std::to_string(set[i]);
+        return s;
+      case kPointer: return "pointer";
+      case kAction: return "action";
+    }
+    return s;
+  }
+};
+template <class... T> constexpr int count_of(T...) { return sizeof...(T); }
+#define SRK_BOOL {Accepts::kBool, 0, 0, {}, 0}
+#define SRK_RANGE(lo, hi) {Accepts::kRange, lo, hi, {}, 0}
+#define SRK_ONEOF(...) {Accepts::kOneOf, 0, 0, {__VA_ARGS__}, count_of(__VA_ARGS__)}
+#define SRK_POINTER {Accepts::kPointer, 0, 0, {}, 0}
+#define SRK_ACTION {Accepts::kAction, 0, 0, {}, 0}
+
+struct Option {
+  const char* name;
+  Accepts accepts;
+  int64_t def;
+  const char* doc;
+  int* i; unsigned* u;       // a plain option's variable (one of the two), or
+  int (*set)(int64_t);       // a hooked option's store
+  int64_t (*get)();          // and read (nullptr: an action)
+  bool readable() const { return i || u || get; }
+  int64_t value() const { return i ? *i : u ? *u : get(); }
+};
+inline Option plain_option(const char* name, Accepts a, int64_t def, const char* doc, int* p) {
+  return {name, a, def, doc, p, nullptr, nullptr, nullptr};
+}
+inline Option plain_option(const char* name, Accepts a, int64_t def, const char* doc, unsigned* p) {
+  return {name, a, def, doc, nullptr, p, nullptr, nullptr};
+}
+#define SRK_PLAIN_ENTRY(type, var, name, accepts, def, doc) plain_option(name, accepts, def, doc, &var),
+#define SRK_HOOKED_ENTRY(name, hook, accepts, def, doc) \
+  Option{name, accepts, def, doc, nullptr, nullptr, option_set_##hook, option_get_##hook},
+const Option g_options[] = {SRK_OPTION_LIST(SRK_PLAIN_ENTRY, SRK_HOOKED_ENTRY)};
+
+const Option* find_option(const char* name) {
+  for (const Option& o : g_options)
+    if (!strcmp(o.name, name)) return &o;
+  return nullptr;
+}
+
+}  // namespace
 }  // namespace srk
 
 extern "C" {
@@ -407,177 +459,44 @@ int srk_init(int device) {
 int srk_set_option(const char* name, int64_t value) {
   SRK_API_BEGIN
   SRK_REQUIRE(name, SRK_ERR_INVALID, "set_option: null name");
-  const std::string n(name);
-  if (n == "release_scratch") {   // free the library's grow-only scratch buffers (invalidates captured graphs)
-    return srk::ScratchPool::release_all();
+  const srk::Option* o = srk::find_option(name);
+  SRK_REQUIRE(o, SRK_ERR_INVALID, "set_option: unknown option '%s'", name);
+  SRK_REQUIRE(o->accepts.ok(value), SRK_ERR_INVALID, "set_option: %s = %lld refused, it accepts %s", name,
+              (long long)value, o->accepts.text().c_str());
+  if (o->set) return o->set(value);
+  const int64_t v = o->accepts.kind == srk::Accepts::kBool ? value != 0 : value;
+  if (o->i) *o->i = (int)v; else *o->u = (unsigned)v;
+  return SRK_OK;
+  SRK_API_END
+}
+
+int srk_get_option(const char* name, int64_t* value) {
+  SRK_API_BEGIN
+  SRK_REQUIRE(name && value, SRK_ERR_INVALID, "get_option: null argument");
+  const srk::Option* o = srk::find_option(name);
+  SRK_REQUIRE(o, SRK_ERR_INVALID, "get_option: unknown option '%s'", name);
+  SRK_REQUIRE(o->readable(), SRK_ERR_INVALID, "get_option: '%s' is an action, it has no value", name);
+  *value = o->value();
+  return SRK_OK;
+  SRK_API_END
+}
+
+int srk_option_list(char* buf, int64_t cap, int64_t* needed) {
+  SRK_API_BEGIN
+  SRK_REQUIRE(needed && (buf || cap == 0), SRK_ERR_INVALID, "option_list: null pointer");
+  std::string out;
+  for (const srk::Option& o : srk::g_options) {
+    const bool action = !o.readable();   // no default and no value: both columns say "action"
+    out += std::string(o.name) + "\t" + (action ? "action" : std::to_string(o.def)) + "\t" +
+           (action ? "action" : std::to_string(o.value())) + "\t" + o.accepts.text() + "\t" + o.doc + "\n";
   }
-  if (n == "gru_persistent") {
-    srk::g_opt_gru_persistent = value != 0;
-    return SRK_OK;
+  *needed = (int64_t)out.size() + 1;
+  if (cap > 0) {
+    const size_t n = std::min<size_t>(out.size(), (size_t)cap - 1);
+    memcpy(buf, out.data(), n);
+    buf[n] = 0;
   }
-  if (n == "conv_fwd_fp32") {   // 16-bit modes: conv forward passes on fp32 operands (1), or 16-bit (0)
-    srk::g_opt_conv_fwd_fp32 = value != 0;
-    return SRK_OK;
-  }
-  if (n == "matmul_precision") {   // 0 fp32, 1 bf16, 2 fp16 matrix-core operands (fp32 accumulate)
-    SRK_REQUIRE(value >= 0 && value <= 2, SRK_ERR_INVALID, "matmul_precision must be 0, 1 or 2");
-    srk::g_opt_matmul_prec.store((int)value);
-    return SRK_OK;
-  }
-  if (n == "gemm16_kernel") {   // 0 by shape, 1 register-staged, 2 LDS-DMA ping-pong (16-bit operands)
-    SRK_REQUIRE(value >= 0 && value <= 2, SRK_ERR_INVALID, "gemm16_kernel must be 0, 1 or 2");
-    srk::g_opt_gemm16_kernel = (int)value;
-    return SRK_OK;
-  }
-  if (n == "gemm_streamk") {   // fp32 ping-pong GEMM: stream-K over a partial round of tiles (1) or not (0)
-    srk::g_opt_gemm_streamk = value != 0;
-    return SRK_OK;
-  }
-  if (n == "mfcc_variant") {   // K1: bit 0 DPP untangle exchange, bit 1 twiddles in registers (bitwise the same)
-    SRK_REQUIRE(value >= 0 && value <= 3, SRK_ERR_INVALID, "mfcc_variant must be 0..3");
-    srk::g_opt_mfcc_variant = (int)value;
-    return SRK_OK;
-  }
-  if (n == "bn_tree") {   // BatchNorm statistics: chunk partials combined as a pairwise tree (1) or in order (0)
-    SRK_REQUIRE(value >= 0 && value <= 2, SRK_ERR_INVALID, "bn_tree must be 0, 1 or 2");
-    srk::g_opt_bn_tree = (int)value;
-    return SRK_OK;
-  }
-  if (n == "conv_ring_qs") {   // 16-bit ring convs: whole K-tiles per MFMA section, mask by width (64, 128, 256)
-    SRK_REQUIRE(value >= 0 && value <= 7, SRK_ERR_INVALID, "conv_ring_qs is a 3-bit mask");
-    srk::g_opt_conv_ring_qs = (int)value;
-    return SRK_OK;
-  }
-  if (n == "conv_row16_dgrad") {   // row-staged conv2 data gradient (1, 2) or the implicit GEMM (0)
-    SRK_REQUIRE(value >= 0 && value <= 2, SRK_ERR_INVALID,
-                "conv_row16_dgrad must be 0, 1 (3 / 3 / 2 / 2 row blocks per wave) or 2 (5 units per wave)");
-    srk::g_opt_conv_row16_dgrad = (int)value;
-    return SRK_OK;
-  }
-  if (n == "conv_row16") {   // fbanks conv2 + pool, 16-bit: row-staged kernel (1) or implicit GEMM (0)
-    SRK_REQUIRE(value >= 0 && value <= 2, SRK_ERR_INVALID, "conv_row16 must be 0, 1 (8 waves) or 2 (4 waves)");
-    srk::g_opt_conv_row16 = (int)value;
-    return SRK_OK;
-  }
-  if (n == "conv_row32") {   // fbanks conv2 on fp32 operands: row-staged kernels (1) or the implicit GEMM (0)
-    srk::g_opt_conv_row32 = value != 0;
-    return SRK_OK;
-  }
-  if (n == "conv_fw_gemm") {   // full-width "valid" conv forward as a plain GEMM (1) or the implicit GEMM (0)
-    srk::g_opt_conv_fw_gemm = value != 0;
-    return SRK_OK;
-  }
-  if (n == "conv_fast16") {   // 16-bit-source register-staged convs: uniform-tap fast gathers (1) or generic (0)
-    srk::g_opt_conv_fast16 = value != 0;
-    return SRK_OK;
-  }
-  if (n == "conv_colsum16") {   // 16-bit modes: conv bias gradients fused into dY's 16-bit conversion (1) or not (0)
-    srk::g_opt_conv_colsum16 = value != 0;
-    return SRK_OK;
-  }
-  if (n == "conv_unpool16") {   // 16-bit modes: pooled-conv backward writes dY's 16-bit copy directly (1) or not (0)
-    srk::g_opt_conv_unpool16 = value != 0;
-    return SRK_OK;
-  }
-  if (n == "conv_ring") {   // ring conv kernels where the shape qualifies: bits 0-2 fp32 fwd / dgrad / wgrad, 4-6 16-bit,
-                            // 7 the pooled forward too
-    SRK_REQUIRE(value >= 0 && value <= 0xf7, SRK_ERR_INVALID,
-                "conv_ring is a mask of 1 / 2 / 4 (fp32 fwd / dgrad / wgrad), 16 / 32 / 64 (16-bit) and 128 "
-                "(the pooled forward too)");
-    srk::g_opt_conv_ring = (int)value;
-    return SRK_OK;
-  }
-  if (n == "conv_tile") {   // 128: 128-row conv tiles (4 waves); 256: 256-row tiles (8 waves) on tall convs
-    SRK_REQUIRE(value == 128 || value == 256, SRK_ERR_INVALID, "conv_tile must be 128 or 256");
-    srk::g_opt_conv_tile = (int)value;
-    return SRK_OK;
-  }
-  if (n == "conv_unpool_gather") {   // pooled conv backward: gathers unpool (1) or a dense scratch gradient (0)
-    srk::g_opt_conv_unpool_gather = value != 0;
-    return SRK_OK;
-  }
-  if (n == "conv_fused_db") {   // conv bias gradients fused into the weight-gradient kernel (1) or a column sum (0)
-    srk::g_opt_conv_fused_db = value != 0;
-    return SRK_OK;
-  }
-  if (n == "conv16_sources") {   // bf16 / fp16 convs gather from a pre-rounded 16-bit copy (1) or round in LDS (0)
-    srk::g_opt_conv16_sources = value != 0;
-    return SRK_OK;
-  }
-  if (n == "gemm32_kernel") {   // 0 by shape, 1 register-staged, 2 LDS-DMA ping-pong (fp32 operands)
-    SRK_REQUIRE(value >= 0 && value <= 2, SRK_ERR_INVALID, "gemm32_kernel must be 0, 1 or 2");
-    srk::g_opt_gemm32_kernel = (int)value;
-    return SRK_OK;
-  }
-  if (n == "gru_spin_limit") {   // test hook: polls before a persistent wait gives up (0 = ~2 s default)
-    SRK_REQUIRE(value >= 0 && value <= 0xffffffffLL, SRK_ERR_INVALID, "gru_spin_limit out of range");
-    srk::g_opt_gru_spin_limit = (unsigned)value;
-    return SRK_OK;
-  }
-  if (n == "gru_xcd_local") {   // persistent GRU: XCD-local hand-off when every XCD hosts one (dir, group)
-    srk::g_opt_gru_xcd_local = value != 0;
-    return SRK_OK;
-  }
-  if (n == "gru_fp32_dual_chain") {   // fp32 recurrence: 8-wave workgroups running two row chains (1) or the 4-wave form (0)
-    srk::g_opt_gru_dc = value != 0;
-    return SRK_OK;
-  }
-  if (n == "gru_dc_offset_ns") {   // fp32 two-chain kernels: delay chain 1's start (phase offset between the chains)
-    SRK_REQUIRE(value >= 0 && value <= 1000000, SRK_ERR_INVALID, "gru_dc_offset_ns out of range");
-    srk::g_opt_gru_dc_offset = (unsigned)(value / 10);
-    return SRK_OK;
-  }
-  if (n == "gru_fwd_worker") {   // 16-bit forward: y / gate stores and the gi fetch on extra worker waves (1) or not (0)
-    srk::g_opt_gru_fwd_worker = value != 0;
-    return SRK_OK;
-  }
-  if (n == "gru_dwhh_fused") {   // 16-bit backward: dW_hh accumulated in the recurrence kernel (bit 0) or by a GEMM (0);
-                                  // bit 1: h_prev fetched after the next exchange barrier, bit 2: recurrence waves at s_setprio 1
-    SRK_REQUIRE(value >= 0 && value <= 7, SRK_ERR_INVALID, "gru_dwhh_fused must be 0..7");
-    srk::g_opt_gru_dwhh_fused = (value & 1) ? (int)value : 0;
-    return SRK_OK;
-  }
-  if (n == "gru_dc_prio") {   // fp32 two-chain kernels: 0 equal priority, 1 / 2 chain 0 / 1 at s_setprio 1 (static)
-    SRK_REQUIRE(value >= 0 && value <= 2, SRK_ERR_INVALID, "gru_dc_prio must be 0, 1 or 2");
-    srk::g_opt_gru_dc_prio = (int)value;
-    return SRK_OK;
-  }
-  if (n == "gru_fp32_fast_cell") {   // fp32 two-chain forward: v_exp_f32 / v_rcp_f32 cell nonlinearities
-    srk::g_opt_gru_fast_cell = value != 0;
-    return SRK_OK;
-  }
-  if (n == "gru_lp_wide") {   // 16-bit recurrence over > 256 rows: 64-row workgroups in one launch (1) or 256-row chunks (0)
-    srk::g_opt_gru_lp_wide = value != 0;
-    return SRK_OK;
-  }
-  if (n == "gemm_skinny") {   // GEMMs with a dimension <= 16 on the VALU kernels (1) or the matrix-core tiles (0)
-    srk::g_opt_gemm_skinny = value != 0;
-    return SRK_OK;
-  }
-  if (n == "attn_pool_regs") {   // attention pooling: register-resident clips where they fit (1) or two passes (0)
-    srk::g_opt_attn_pool_regs = value != 0;
-    return SRK_OK;
-  }
-  if (n == "gru_dwhh_batched") {   // 16-bit GRU backward: both directions' dW_hh in one batched GEMM (1) or two (0)
-    srk::g_opt_gru_dwhh_batched = value != 0;
-    return SRK_OK;
-  }
-  if (n == "gru_top_last") {   // srk_gru_top_last_* on the fp32 persistent path: 0 the full layer, 1 the backward GEMMs
-                               // pruned, 2 also the reverse direction as one cell, 3 that cell with the full dW_ih /
-                               // dx GEMMs: the full layer's bits (default)
-    SRK_REQUIRE(value >= 0 && value <= 3, SRK_ERR_INVALID, "gru_top_last must be 0 .. 3");
-    srk::g_opt_gru_top_last = (int)value;
-    return SRK_OK;
-  }
-  if (n == "gru_lp_32x32") {   // 16-bit recurrence: 32 x 32 workgroups (1) or 64 rows x 16 units (0)
-    srk::g_opt_gru_lp2 = value != 0;
-    return SRK_OK;
-  }
-  if (n == "gru_trace_ptr") {   // diagnostics: device buffer of 8 x u64 per (workgroup, step), 0 = off
-    srk::g_opt_gru_trace = reinterpret_cast<unsigned long long*>(value);
-    return SRK_OK;
-  }
-  SRK_REQUIRE(false, SRK_ERR_INVALID, "set_option: unknown option '%s'", name);
+  return SRK_OK;
   SRK_API_END
 }
 

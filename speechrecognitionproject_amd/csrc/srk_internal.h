@@ -8,6 +8,7 @@
 #include <string>
 
 #include "../../include/srk.h"
+#include "options.h"
 
 namespace srk {
 
@@ -93,14 +94,7 @@ struct PrecScope {
   }
   ~PrecScope() { t_prec_override = saved; }
 };
-// 16-bit modes: every convolution FORWARD pass on fp32 operands, the data / weight gradients on 16-bit ones
-// ("conv_fwd_fp32", default 0).  resnet_bgru's training-mode BatchNorm chain amplifies the forward's operand
-// rounding into 4-39 % norm-wise gradient errors, while 16-bit gradients alone stay <= 0.9 %
-// (tools/bf16_policy_resnet.py): the faithful 16-bit training mode of the BatchNorm models.
-extern int g_opt_conv_fwd_fp32;
 
-// Kernel of the 16-bit-operand GEMM (srk_set_option "gemm16_kernel", A/B measurements and tests):
-// 0 = by shape, 1 = register-staged gemm_h16_kernel, 2 = LDS-DMA ping-pong gemm_g16_kernel.
 // Bumped whenever a library scratch buffer is (re)allocated: a captured HIP graph that refers to the
 // old buffer must not be replayed (srk_scratch_generation; graphs.GraphedStep checks it).
 extern std::atomic<int64_t> g_scratch_gen;
@@ -127,69 +121,17 @@ class ScratchPool {
   ScratchPool* next_;           // the instances, linked as they are constructed
   static ScratchPool* head_;
 };
-extern int g_opt_gemm16_kernel;
-// Kernel of the fp32 GEMM (srk_set_option "gemm32_kernel"): 0 = by shape, 1 = register-staged
-// gemm_f32_kernel, 2 = LDS-DMA ping-pong gemm_p32_kernel.
-extern int g_opt_gemm32_kernel;
-extern int g_opt_gru_dwhh_batched;
-extern int g_opt_gemm_skinny;   // GEMMs with a dimension <= 16 on the VALU skinny kernels   // 16-bit GRU backward: one batched dW_hh GEMM for both directions
-// 16-bit conv operand sources (srk_set_option "conv16_sources", default 1): bf16 / fp16 convolutions
-// gather from one pre-rounded 16-bit copy of x / dY / the weights (0 = round at LDS-store time).
-extern int g_opt_conv16_sources;
-// conv bias gradients as column sums fused into the weight-gradient kernel ("conv_fused_db", default
-// 1; 0 = the separate column-sum kernel over dY)
-extern int g_opt_conv_fused_db;
-// the pooled conv's backward gathers the pooled gradient through the argmax ("conv_unpool_gather",
-// default 1; 0 = unpool into library scratch first)
-extern int g_opt_conv_unpool_gather;
-// 16-bit-source modes: the pooled conv's backward writes the dense dY straight as its 16-bit copy
-// ("conv_unpool16", default 1; 0 = dense fp32 dY, then the 16-bit conversion and column sums)
-extern int g_opt_conv_unpool16;
-// 16-bit-source modes: the conv bias gradient (column sums of dY) fused into the pass that rounds dY (or
-// unpools it) to its 16-bit copy ("conv_colsum16", default 1; 0 = a separate column-sum pass over dY)
-extern int g_opt_conv_colsum16;
-// 16-bit ring convs: whole 32-deep K-tiles per MFMA section (QS 2) by tile width, a mask ("conv_ring_qs": bit 1
-// BN 128, bit 2 BN 256; default 6)
-extern int g_opt_conv_ring_qs;
-// register-staged 16-bit-source convs (fwd / dgrad): uniform-tap gathers with per-row bases and zero-filling
-// buffer loads where the channels are a multiple of the K-tile ("conv_fast16", default 1)
-extern int g_opt_conv_fast16;
-// fbanks_cnn conv2 + maxpool2 in 16-bit modes on the row-staged kernel (weights resident in LDS, image rows staged
-// once per tile) ("conv_row16", default 1; 0 = the implicit-GEMM kernels)
-extern int g_opt_conv_row16;
-// fbanks_cnn conv2 (+ maxpool2) on fp32 operands on the row-staged kernels (x rows staged once per tile, the weights
-// streamed one tap at a time) ("conv_row32", default 1; 0 = the implicit-GEMM kernels)
-extern int g_opt_conv_row32;
-// a full-width "valid" conv's forward (fbanks_cnn conv3, (1, 10) over width 10) as the plain GEMM x . Wt + bias
-// ("conv_fw_gemm", default 1; 0 = the implicit GEMM)
-extern int g_opt_conv_fw_gemm;
-// the row-staged data gradient of the same conv ("conv_row16_dgrad", default 2 = 5 units per wave; 1 = 3 / 3 / 2 / 2
-// row blocks per wave, 418 vs 475-485 us, r05p; 0 = the implicit GEMM)
-extern int g_opt_conv_row16_dgrad;
-// BatchNorm training statistics: the <= 256 chunk partials combined in chunk order, the count ratios off the
-// dependent chain ("bn_tree" 0, default); 1 = a fixed pairwise tree, one wave per channel (more accurate, but
-// other bits than the reference's in-order arithmetic: ReLU decisions on values within roundoff of 0 move —
-// tests/test_conv_gpu.py golden resnet_bgru at B = 2); 2 = in order with the divides in the chain (form 0's
-// bitwise reference)
-extern int g_opt_bn_tree;
-// conv tile shape ("conv_tile": 128 = 128-row tiles of 4 waves, 256 = 256-row tiles of 8 waves on
-// tall convolutions)
-extern int g_opt_conv_tile;
-// LDS-DMA ring implicit-GEMM convolutions where the shape qualifies ("conv_ring": a mask of
-// 1 / 2 / 4 = fp32 forward / data gradient / weight gradient, 16 / 32 / 64 = the same on 16-bit
-// operands, 128 = the forward with the pooled epilogue and the fp32 forward at K < 3072 too; default
-// 0x77 — measured, r04ab / r04ab3 / r04ab6: the pooled ring forward slower in both precisions, the fp32
-// ring forward faster on the deep-K ResNet layers only)
-extern int g_opt_conv_ring;
-// K1 MFCC variant ("mfcc_variant", bitwise-identical outputs): bit 0 = the untangle's partner exchange
-// by DPP row_mirror instead of ds_bpermute, bit 1 = twiddles in registers instead of LDS (default 3)
-extern int g_opt_mfcc_variant;
-// stream-K for fp32 ping-pong GEMMs whose 256 x 256 grid covers 1/2 .. 1 round of CUs ("gemm_streamk",
-// default 1)
-extern int g_opt_gemm_streamk;
-// attention pooling: clips that fit the register file are read once ("attn_pool_regs", default 1; 0 = every shape
-// on the two-pass kernel)
-extern int g_opt_attn_pool_regs;
+
+// Runtime options (srk_set_option): options.h states each one once; these are its variables, defined in runtime.hip.
+#define SRK_DECLARE_OPTION(type, var, name, accepts, def, doc) extern type var;
+#define SRK_HOOKED_OPTION(name, hook, accepts, def, doc)
+SRK_OPTION_LIST(SRK_DECLARE_OPTION, SRK_HOOKED_OPTION)
+#undef SRK_DECLARE_OPTION
+#undef SRK_HOOKED_OPTION
+// What the hooked options store (matmul_precision: matmul_prec() above).
+extern unsigned long long* g_opt_gru_trace;   // "gru_trace_ptr": device buffer or nullptr
+extern unsigned g_opt_gru_dc_offset;          // "gru_dc_offset_ns" in ticks of 10 ns
+extern int g_opt_gru_dwhh_fused;              // "gru_dwhh_fused": 0, or an odd value (bit 0 = fused)
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 

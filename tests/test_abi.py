@@ -61,3 +61,8 @@ def test_new_entry_points_reject_bad_arguments():
     rc = L.srk_conv2d_nhwc_fwd_pool(ctypes.c_void_p(256), 2, 98, 40, 64, ctypes.c_void_p(256), None, 128, 1, 7, 0, 3,
                                     3, ctypes.c_void_p(256), ctypes.c_void_p(256), ctypes.c_void_p(256), None, None, None)
     assert rc != 0 and b"window" in L.srk_last_error()
+    # the option readers: null pointers are refused, a null buffer only with cap 0 (the size query)
+    v = i64(0)
+    assert L.srk_get_option(b"conv_ring", None) == -1 and L.srk_get_option(None, ctypes.byref(v)) == -1
+    assert L.srk_option_list(None, 16, ctypes.byref(v)) == -1 and L.srk_option_list(None, 0, None) == -1
+    assert L.srk_option_list(None, 0, ctypes.byref(v)) == 0 and v.value > 0

@@ -99,11 +99,8 @@ def test_attn_pool_vs_float64(gpu, case):
 def test_attn_pool_two_pass_kernel_on_register_shapes(gpu, case):
     """attn_pool_regs = 0: the two-pass kernel takes the shapes the register-resident one usually does (its float4
     path at small T and D, every row-group count of its column sums), to the same bound."""
-    try:
-        _lib.set_option("attn_pool_regs", 0)
+    with _lib.options(attn_pool_regs=0):
         _check_parity(case, "attn_pool_2pass_kernel")
-    finally:
-        _lib.set_option("attn_pool_regs", 1)
 
 
 def test_attn_pool_overflow_guard(gpu):

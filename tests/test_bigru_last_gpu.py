@@ -9,7 +9,6 @@ that reach every branch: T = 1 (K = B T - 1 = 0 in dW_hh), a partial 64-row grou
 Off the fp32 persistent path the entry points run the full layer, so there the results equal
 last_step(forward(x)[0]) bit for bit.
 """
-import contextlib
 import ctypes
 import functools
 
@@ -31,13 +30,8 @@ MODES = [1, 2, 3]
 DEFAULT_MODE = 3
 
 
-@contextlib.contextmanager
 def _mode(mode):
-    _lib.set_option("gru_top_last", mode)
-    try:
-        yield
-    finally:
-        _lib.set_option("gru_top_last", DEFAULT_MODE)
+    return _lib.options(gru_top_last=mode)
 
 
 def _inputs(layers, IN, H, B, T, seed):
@@ -213,11 +207,8 @@ def test_forward_last_16bit_is_the_full_layer(gpu, precision):
 
 @pytest.mark.gpu
 def test_forward_last_without_persistent_kernels_is_the_full_layer(gpu):
-    try:
-        _lib.set_option("gru_persistent", 0)
+    with _lib.options(gru_persistent=0):
         _bitwise_vs_full(2, 39, 512, 8, 4)
-    finally:
-        _lib.set_option("gru_persistent", 1)
 
 
 @pytest.mark.gpu

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from speechrecognitionproject_amd._lib import call, set_option
+from speechrecognitionproject_amd._lib import call, options
 from speechrecognitionproject_amd.features import ptr, stream_ptr
 
 pytestmark = pytest.mark.gpu
@@ -34,12 +34,9 @@ def test_finalize_in_order_forms_bitwise(gpu, M, C):
     g = torch.Generator().manual_seed(M + C)
     x = (torch.randn(M, C, generator=g) * 0.7 + torch.randn(C, generator=g) * 3).cuda()
     out = {}
-    try:
-        for form in (0, 2, 1):
-            set_option("bn_tree", form)
+    for form in (0, 2, 1):
+        with options(bn_tree=form):
             out[form] = _fwd(x, M, C)
-    finally:
-        set_option("bn_tree", 0)
     for a, b in zip(out[0], out[2]):
         assert torch.equal(a, b)
     x64 = x.double().cpu()

@@ -221,19 +221,18 @@ def _lowprec_step(net, x, y, precision="bf16", conv_fwd_fp32=False):
     opt = Adam(net.parameters(), lr=LR, flat=flat)
     try:
         _lib.set_matmul_precision(precision)
-        _lib.set_option("conv_fwd_fp32", 1 if conv_fwd_fp32 else 0)
-        opt.zero_grad()
-        out = net(torch.from_numpy(x).cuda())
-        loss = snn.CrossEntropyLoss()(out, torch.from_numpy(y).cuda())
-        loss.backward()
-        torch.cuda.synchronize()
-        grads = {n: p.grad.detach().cpu().clone() for n, p in net.named_parameters() if p.grad is not None}
-        p0 = {n: p.detach().cpu().clone() for n, p in net.named_parameters()}
-        opt.step()
-        torch.cuda.synchronize()
+        with _lib.options(conv_fwd_fp32=1 if conv_fwd_fp32 else 0):
+            opt.zero_grad()
+            out = net(torch.from_numpy(x).cuda())
+            loss = snn.CrossEntropyLoss()(out, torch.from_numpy(y).cuda())
+            loss.backward()
+            torch.cuda.synchronize()
+            grads = {n: p.grad.detach().cpu().clone() for n, p in net.named_parameters() if p.grad is not None}
+            p0 = {n: p.detach().cpu().clone() for n, p in net.named_parameters()}
+            opt.step()
+            torch.cuda.synchronize()
     finally:
         _lib.set_matmul_precision("fp32")
-        _lib.set_option("conv_fwd_fp32", 0)
     assert _lib.spin_timeouts() == 0 and opt.step_count == 1
     return out.detach().cpu().numpy(), float(loss.item()), grads, p0
 

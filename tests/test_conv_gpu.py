@@ -59,11 +59,8 @@ def test_conv2d_nhwc_vs_torch(gpu, shape):
 def test_conv2d_tile256_vs_torch(gpu, shape):
     """srk option conv_tile = 256: the 256-row, 8-wave conv tiles (fp32) on tall convolutions."""
     from speechrecognitionproject_amd import _lib
-    try:
-        _lib.set_option("conv_tile", 256)
+    with _lib.options(conv_tile=256):
         _check_conv(*shape)
-    finally:
-        _lib.set_option("conv_tile", 128)
 
 
 @pytest.mark.parametrize("shape", [(2, 98, 40, 64, 128, 1, 7, 0, 3), (3, 98, 1, 256, 512, 7, 1, 3, 0),
@@ -74,11 +71,8 @@ def test_conv2d_ring_vs_torch(gpu, shape):
     per-K-tile conv gathers, direct epilogue, fused bias sums) wherever the shape qualifies (channel
     counts % 16, >= 128 output columns, stride 1 for the data gradient); the rest as before."""
     from speechrecognitionproject_amd import _lib
-    try:
-        _lib.set_option("conv_ring", 0x87)   # every qualifying shape, any K
+    with _lib.options(conv_ring=0x87):   # every qualifying shape, any K
         _check_conv(*shape)
-    finally:
-        _lib.set_option("conv_ring", 0x77)
 
 
 @pytest.mark.parametrize("shape", [  # 1-D strided convs of model_resnet_bgru.py:48,19-23 as H=1
@@ -200,24 +194,20 @@ def test_conv_pool_fused_equals_separate(gpu, gather, ring, precision, N, H, W, 
     outs = []
     try:
         _lib.set_matmul_precision(precision)
-        _lib.set_option("conv_unpool_gather", gather)
-        _lib.set_option("conv_ring", ring)
-        _lib.set_option("conv_row32", 0)   # the implicit-GEMM paths (row-staged: test_conv_row32_equals_gemm)
-        for fused in (True, False):
-            _lib.set_fused_conv_pool(fused)
-            with torch.no_grad():
-                conv.weight.copy_(w)
-                conv.bias.copy_(b)
-            conv.weight.grad = conv.bias.grad = None
-            xm = x.cuda().requires_grad_(True)
-            y = snn.conv_pool(xm, conv, pool)
-            (y * gy.cuda()).sum().backward()
-            torch.cuda.synchronize()
-            outs.append([t.detach().cpu() for t in (y, xm.grad, conv.weight.grad, conv.bias.grad)])
+        # conv_row32 = 0: the implicit-GEMM paths (row-staged: test_conv_row32_equals_gemm)
+        with _lib.options(conv_unpool_gather=gather, conv_ring=ring, conv_row32=0):
+            for fused in (True, False):
+                _lib.set_fused_conv_pool(fused)
+                with torch.no_grad():
+                    conv.weight.copy_(w)
+                    conv.bias.copy_(b)
+                conv.weight.grad = conv.bias.grad = None
+                xm = x.cuda().requires_grad_(True)
+                y = snn.conv_pool(xm, conv, pool)
+                (y * gy.cuda()).sum().backward()
+                torch.cuda.synchronize()
+                outs.append([t.detach().cpu() for t in (y, xm.grad, conv.weight.grad, conv.bias.grad)])
     finally:
-        _lib.set_option("conv_unpool_gather", 1)
-        _lib.set_option("conv_ring", 0x77)
-        _lib.set_option("conv_row32", 1)
         _lib.set_fused_conv_pool(True)
         _lib.set_matmul_precision("fp32")
     row_wgrad = (W, Ci, Co, KH, KW, ph, pw) == (40, 64, 128, 1, 7, 0, 3)   # fbanks_cnn conv2's shape
@@ -257,13 +247,12 @@ def test_conv_bias_grad_fused_into_wgrad(gpu, precision):
     try:
         _lib.set_matmul_precision(precision)
         for fused in (1, 0):
-            _lib.set_option("conv_fused_db", fused)
-            xm, wm, bm = x.clone().requires_grad_(True), w.clone().requires_grad_(True), b.clone().requires_grad_(True)
-            (snn._Conv2dNHWCFn.apply(xm, wm, bm, (ph, pw), (1, 1)) * gy).sum().backward()
-            torch.cuda.synchronize()
-            res.append((xm.grad.cpu(), wm.grad.cpu(), bm.grad.cpu()))
+            with _lib.options(conv_fused_db=fused):
+                xm, wm, bm = x.clone().requires_grad_(True), w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+                (snn._Conv2dNHWCFn.apply(xm, wm, bm, (ph, pw), (1, 1)) * gy).sum().backward()
+                torch.cuda.synchronize()
+                res.append((xm.grad.cpu(), wm.grad.cpu(), bm.grad.cpu()))
     finally:
-        _lib.set_option("conv_fused_db", 1)
         _lib.set_matmul_precision("fp32")
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
     want = gy.double().sum(dim=(0, 1, 2)).cpu()
@@ -447,18 +436,17 @@ def test_conv_pool_unpool16(gpu, prec, N, H, W, Ci, Co, KH, KW, ph, pw):
     try:
         _lib.set_matmul_precision(prec)
         for u16 in (1, 0):
-            _lib.set_option("conv_unpool16", u16)
-            with torch.no_grad():
-                conv.weight.copy_(w)
-                conv.bias.copy_(b)
-            conv.weight.grad = conv.bias.grad = None
-            xm = x.cuda().requires_grad_(True)
-            y = snn.conv_pool(xm, conv, pool)
-            (y * gy).sum().backward()
-            torch.cuda.synchronize()
-            outs.append([t.detach().cpu() for t in (y, xm.grad, conv.weight.grad, conv.bias.grad)])
+            with _lib.options(conv_unpool16=u16):
+                with torch.no_grad():
+                    conv.weight.copy_(w)
+                    conv.bias.copy_(b)
+                conv.weight.grad = conv.bias.grad = None
+                xm = x.cuda().requires_grad_(True)
+                y = snn.conv_pool(xm, conv, pool)
+                (y * gy).sum().backward()
+                torch.cuda.synchronize()
+                outs.append([t.detach().cpu() for t in (y, xm.grad, conv.weight.grad, conv.bias.grad)])
     finally:
-        _lib.set_option("conv_unpool16", 1)
         _lib.set_matmul_precision("fp32")
     row_wgrad = (W, Ci, Co, KH, KW, ph, pw) == (40, 64, 128, 1, 7, 0, 3)
     for i, (a, c) in enumerate(zip(*outs)):
@@ -487,16 +475,15 @@ def test_conv_row32_equals_gemm(gpu, N):
     outs = []
     try:
         for row in (1, 0):
-            _lib.set_option("conv_row32", row)
-            _lib.prof_enable(True)
-            with torch.no_grad():
-                y = snn._ConvPoolNHWCFn.apply(x, w, b, (0, 3), 4)
-            torch.cuda.synchronize()
-            used = any("conv_row32" in e["kernel"] for e in _lib.prof_kernels())
-            _lib.prof_enable(False)
-            outs.append((y, used))
+            with _lib.options(conv_row32=row):
+                _lib.prof_enable(True)
+                with torch.no_grad():
+                    y = snn._ConvPoolNHWCFn.apply(x, w, b, (0, 3), 4)
+                torch.cuda.synchronize()
+                used = any("conv_row32" in e["kernel"] for e in _lib.prof_kernels())
+                _lib.prof_enable(False)
+                outs.append((y, used))
     finally:
-        _lib.set_option("conv_row32", 1)
         _lib.prof_enable(False)
     (y1, u1), (y0, u0) = outs
     assert u1 and not u0
@@ -512,17 +499,16 @@ def test_conv_row32_equals_gemm(gpu, N):
     grads = []
     try:
         for row in (1, 0):
-            _lib.set_option("conv_row32", row)
-            _lib.prof_enable(True)
-            xm, wm, bm = (t.clone().requires_grad_(True) for t in (x, w, b))
-            (snn._ConvPoolNHWCFn.apply(xm, wm, bm, (0, 3), 4) * gy).sum().backward()
-            torch.cuda.synchronize()
-            ks = [e["kernel"] for e in _lib.prof_kernels()]
-            used = any("conv_row32_dgrad" in k for k in ks) and any("conv_row32_wgrad" in k for k in ks)
-            _lib.prof_enable(False)
-            grads.append((xm.grad, wm.grad, bm.grad, used))
+            with _lib.options(conv_row32=row):
+                _lib.prof_enable(True)
+                xm, wm, bm = (t.clone().requires_grad_(True) for t in (x, w, b))
+                (snn._ConvPoolNHWCFn.apply(xm, wm, bm, (0, 3), 4) * gy).sum().backward()
+                torch.cuda.synchronize()
+                ks = [e["kernel"] for e in _lib.prof_kernels()]
+                used = any("conv_row32_dgrad" in k for k in ks) and any("conv_row32_wgrad" in k for k in ks)
+                _lib.prof_enable(False)
+                grads.append((xm.grad, wm.grad, bm.grad, used))
     finally:
-        _lib.set_option("conv_row32", 1)
         _lib.prof_enable(False)
     assert grads[0][3] and not grads[1][3]
     # every gradient on the row-staged kernels (data: conv_row32_dgrad_kernel; weight and bias:
@@ -569,18 +555,17 @@ def test_conv_full_width_fwd_gemm(gpu, prec, N):
     _lib.set_matmul_precision(prec)
     try:
         for on in (1, 0):
-            _lib.set_option("conv_fw_gemm", on)
-            _lib.prof_enable(True)
-            with torch.no_grad():
-                y = snn._Conv2dNHWCFn.apply(x, w, b, (0, 0), (1, 1))
-            torch.cuda.synchronize()
-            # the plain GEMM's launch (innermost profiling scope: M x N x K = N H x Co x W Ci)
-            used = any(e["kernel"].startswith("gemm_") and "%dx%dx%d" % (N * H, Co, W * Ci) in e["kernel"]
-                       for e in _lib.prof_kernels())
-            _lib.prof_enable(False)
-            ys.append((y.double(), used))
+            with _lib.options(conv_fw_gemm=on):
+                _lib.prof_enable(True)
+                with torch.no_grad():
+                    y = snn._Conv2dNHWCFn.apply(x, w, b, (0, 0), (1, 1))
+                torch.cuda.synchronize()
+                # the plain GEMM's launch (innermost profiling scope: M x N x K = N H x Co x W Ci)
+                used = any(e["kernel"].startswith("gemm_") and "%dx%dx%d" % (N * H, Co, W * Ci) in e["kernel"]
+                           for e in _lib.prof_kernels())
+                _lib.prof_enable(False)
+                ys.append((y.double(), used))
     finally:
-        _lib.set_option("conv_fw_gemm", 1)
         _lib.set_matmul_precision("fp32")
         _lib.prof_enable(False)
     (y1, u1), (y0, u0) = ys

@@ -88,14 +88,13 @@ def test_dilated_conv1d_ring_vs_torch(gpu, case):
     """conv_ring = 0x87: the fp32 LDS-DMA ring kernels at any K — the head's shapes qualify in all three modes
     (channel counts % 16, >= 128 output columns, stride 1), and the ring kernels take dilation."""
     try:
-        _lib.set_option("conv_ring", 0x87)
-        _lib.prof_enable(1)
-        _check_case(case)
-        torch.cuda.synchronize()
-        ks = _kernels()
+        with _lib.options(conv_ring=0x87):
+            _lib.prof_enable(1)
+            _check_case(case)
+            torch.cuda.synchronize()
+            ks = _kernels()
     finally:
         _lib.prof_enable(0)
-        _lib.set_option("conv_ring", 0x77)
     for mode in ("fwd", "dgrad", "wgrad"):
         assert "conv_ring_kernel<%s" % mode in ks, (mode, ks)
 

@@ -56,22 +56,21 @@ def test_gemm_skinny(gpu, precision, ta, tb, M, N, K):
     outs = []
     try:
         for skinny in (1, 0):
-            _lib.set_option("gemm_skinny", skinny)
-            _lib.prof_enable(1)
-            Cd = C0.clone().cuda()
-            call("srk_gemm_f32", ta, tb, M, N, K, 0.5, ptr(Ad), Ad.shape[1], ptr(Bd), Bd.shape[1], 2.0, ptr(Cd), N,
-                 ptr(bias.cuda()), 1, stream_ptr())
-            rs = torch.full((M,), 3.0, device="cuda")
-            Cr = torch.zeros(M, N, device="cuda")
-            call("srk_gemm_rowsum_f32", ta, tb, M, N, K, 1.0, ptr(Ad), Ad.shape[1], ptr(Bd), Bd.shape[1], 0.0,
-                 ptr(Cr), N, ptr(rs), stream_ptr())
-            torch.cuda.synchronize()
-            kinds = [k["kernel"] for k in _lib.prof_kernels()]
-            _lib.prof_enable(0)
-            assert all(("skinny" in k) == bool(skinny) for k in kinds), kinds
-            outs.append((Cd.cpu().double(), rs.cpu().double()))
+            with _lib.options(gemm_skinny=skinny):
+                _lib.prof_enable(1)
+                Cd = C0.clone().cuda()
+                call("srk_gemm_f32", ta, tb, M, N, K, 0.5, ptr(Ad), Ad.shape[1], ptr(Bd), Bd.shape[1], 2.0, ptr(Cd), N,
+                     ptr(bias.cuda()), 1, stream_ptr())
+                rs = torch.full((M,), 3.0, device="cuda")
+                Cr = torch.zeros(M, N, device="cuda")
+                call("srk_gemm_rowsum_f32", ta, tb, M, N, K, 1.0, ptr(Ad), Ad.shape[1], ptr(Bd), Bd.shape[1], 0.0,
+                     ptr(Cr), N, ptr(rs), stream_ptr())
+                torch.cuda.synchronize()
+                kinds = [k["kernel"] for k in _lib.prof_kernels()]
+                _lib.prof_enable(0)
+                assert all(("skinny" in k) == bool(skinny) for k in kinds), kinds
+                outs.append((Cd.cpu().double(), rs.cpu().double()))
     finally:
-        _lib.set_option("gemm_skinny", 1)
         _lib.set_matmul_precision("fp32")
     for c, r in outs:
         assert (c - ref).abs().max().item() <= tol
@@ -169,8 +168,7 @@ def test_gemm_f32_kernels_at_tile_edges(gpu, kernel, ta, tb, M, N, K):
     ref = 0.5 * (opA @ opB) + 2.0 * C0.double() + bias.double()
     tol = 1e-5 * (1 + (opA.abs() @ opB.abs()).max().item())
     Ad, Bd = A.cuda(), B.cuda()
-    _lib.set_option("gemm32_kernel", kernel)
-    try:
+    with _lib.options(gemm32_kernel=kernel):
         Cd = C0.clone().cuda()
         call("srk_gemm_f32", ta, tb, M, N, K, 0.5, ptr(Ad), Ad.shape[1], ptr(Bd), Bd.shape[1], 2.0, ptr(Cd), N,
              ptr(bias.cuda()), 1, stream_ptr())
@@ -179,8 +177,6 @@ def test_gemm_f32_kernels_at_tile_edges(gpu, kernel, ta, tb, M, N, K):
         call("srk_gemm_rowsum_f32", ta, tb, M, N, K, 1.0, ptr(Ad), Ad.shape[1], ptr(Bd), Bd.shape[1], 1.0, ptr(Cr),
              N, ptr(rs), stream_ptr())   # beta = 1 on C (zero-initialised below) and on the row sums
         torch.cuda.synchronize()
-    finally:
-        _lib.set_option("gemm32_kernel", 0)
     assert (Cd.cpu().double() - ref).abs().max().item() <= tol
     assert (rs.cpu().double() - (3.0 + opA.sum(1))).abs().max().item() <= 1e-3 * (1 + K ** 0.5)
 
@@ -232,15 +228,14 @@ def test_bigru_xcd_local_handoff_is_bitwise_identical(gpu, prec, B, T, IN):
     try:
         _lib.set_matmul_precision(prec)
         for mode in (1, 0):
-            _lib.set_option("gru_xcd_local", mode)
-            for _ in range(2):   # twice: the census and the flags must reset between launches
-                mine.zero_grad()
-                xm = x.cuda().requires_grad_(True)
-                ym, _ = mine(xm)
-                (ym * w.cuda()).sum().backward()
-            outs[mode] = [ym.detach().cpu(), xm.grad.cpu()] + [p.grad.cpu() for p in mine.parameters()]
+            with _lib.options(gru_xcd_local=mode):
+                for _ in range(2):   # twice: the census and the flags must reset between launches
+                    mine.zero_grad()
+                    xm = x.cuda().requires_grad_(True)
+                    ym, _ = mine(xm)
+                    (ym * w.cuda()).sum().backward()
+                outs[mode] = [ym.detach().cpu(), xm.grad.cpu()] + [p.grad.cpu() for p in mine.parameters()]
     finally:
-        _lib.set_option("gru_xcd_local", 1)
         _lib.set_matmul_precision("fp32")
     assert _lib.spin_timeouts() == 0
     for i, (a, b) in enumerate(zip(outs[1], outs[0])):
@@ -262,16 +257,13 @@ def test_bigru_persistent_matches_per_step_and_torch(gpu, B, T):
     x = torch.randn(B, T, IN)
     w = torch.randn(B, T, 2 * H)
     outs = {}
-    try:
-        for mode in (1, 0):
-            _lib.set_option("gru_persistent", mode)
+    for mode in (1, 0):
+        with _lib.options(gru_persistent=mode):
             mine.zero_grad()
             xm = x.cuda().requires_grad_(True)
             ym, _ = mine(xm)
             (ym * w.cuda()).sum().backward()
             outs[mode] = [ym.detach().cpu(), xm.grad.cpu()] + [p.grad.cpu() for p in mine.parameters()]
-    finally:
-        _lib.set_option("gru_persistent", 1)
     assert _lib.spin_timeouts() == 0
     for i, (a, b) in enumerate(zip(outs[1], outs[0])):
         err = float((a - b).abs().max() / (b.abs().max() + 1e-30))
@@ -367,19 +359,14 @@ def test_bigru_fp32_dual_chain_matches_four_wave(gpu, B, T, IN):
     x = torch.randn(B, T, IN)
     w = torch.randn(B, T, 2 * H)
     outs = {}
-    try:
-        # (two-chain, static chain priority): the priority (option gru_dc_prio) changes timing only
-        for mode, prio in ((1, 0), (1, 0), (0, 0), (1, 1), (1, 2)):
-            _lib.set_option("gru_fp32_dual_chain", mode)
-            _lib.set_option("gru_dc_prio", prio)
+    # (two-chain, static chain priority): the priority (option gru_dc_prio) changes timing only
+    for mode, prio in ((1, 0), (1, 0), (0, 0), (1, 1), (1, 2)):
+        with _lib.options(gru_fp32_dual_chain=mode, gru_dc_prio=prio):
             mine.zero_grad()
             xm = x.cuda().requires_grad_(True)
             ym, _ = mine(xm)
             (ym * w.cuda()).sum().backward()
             outs.setdefault(mode, []).append([ym.detach().cpu(), xm.grad.cpu()] + [p.grad.cpu() for p in mine.parameters()])
-    finally:
-        _lib.set_option("gru_fp32_dual_chain", 1)
-        _lib.set_option("gru_dc_prio", 0)
     assert _lib.spin_timeouts() == 0
     for k in (1, 2, 3):
         for a, b in zip(outs[1][0], outs[1][k]):
@@ -412,19 +399,18 @@ def test_bigru_lowprec_wide_matches_chunked(gpu, prec, B, T, IN):
     try:
         _lib.set_matmul_precision(prec)
         for mode in (1, 1, 0):
-            _lib.set_option("gru_lp_wide", mode)
-            _lib.prof_enable(True)
-            mine.zero_grad()
-            xm = x.cuda().requires_grad_(True)
-            ym, _ = mine(xm)
-            (ym * w.cuda()).sum().backward()
-            torch.cuda.synchronize()
-            kinds = {r["kernel"].split(" ")[0] for r in _lib.prof_kernels() if r["name"].startswith("gru_")}
-            _lib.prof_enable(False)
-            outs.setdefault(mode, []).append(([ym.detach().cpu(), xm.grad.cpu()],
-                                              dict((n, p.grad.cpu()) for n, p in mine.named_parameters()), kinds))
+            with _lib.options(gru_lp_wide=mode):
+                _lib.prof_enable(True)
+                mine.zero_grad()
+                xm = x.cuda().requires_grad_(True)
+                ym, _ = mine(xm)
+                (ym * w.cuda()).sum().backward()
+                torch.cuda.synchronize()
+                kinds = {r["kernel"].split(" ")[0] for r in _lib.prof_kernels() if r["name"].startswith("gru_")}
+                _lib.prof_enable(False)
+                outs.setdefault(mode, []).append(([ym.detach().cpu(), xm.grad.cpu()],
+                                                  dict((n, p.grad.cpu()) for n, p in mine.named_parameters()), kinds))
     finally:
-        _lib.set_option("gru_lp_wide", 1)
         _lib.set_matmul_precision("fp32")
     assert _lib.spin_timeouts() == 0
     assert "gru_bwd_persistent_lp2w_kernel" in outs[1][0][2] and "gru_bwd_persistent_lp2w_kernel" not in outs[0][0][2]
@@ -462,15 +448,12 @@ def test_gemm_streamk(gpu, M, N, K, ta, beta, bias):
         ref += bv.double()[:, None]
     Ad, Bd, bd = A.cuda(), B.cuda(), bv.cuda()
     outs = []
-    try:
-        for sk in (1, 0):
-            _lib.set_option("gemm_streamk", sk)
+    for sk in (1, 0):
+        with _lib.options(gemm_streamk=sk):
             Cd = C0.clone().cuda()
             call("srk_gemm_f32", ta, 0, M, N, K, 0.5, ptr(Ad), Ad.shape[1], ptr(Bd), N, beta, ptr(Cd), N,
                  ptr(bd) if bias else None, bias, stream_ptr())
             outs.append(Cd.cpu().double())
-    finally:
-        _lib.set_option("gemm_streamk", 1)
     tol = 1e-5 * (1 + (A.abs().max() * B.abs().max() * K).item())
     assert (outs[0] - ref).abs().max() <= tol
     assert (outs[0] - outs[1]).abs().max() <= tol
@@ -518,25 +501,22 @@ def test_gemm_runs_what_the_plan_describes(gpu, entry, opts, prec, ta, tb, M, N,
     buf = ctypes.create_string_buffer(512)
     try:
         _lib.set_matmul_precision(prec)
-        for k, v in opts.items():
-            _lib.set_option(k, v)
-        call("srk_gemm_plan_describe", ta, tb, M, N, K, ac, bc, N, batch, sA, sB, sC, bias, int(entry == "rowsum"),
-             int(o16), -1, 0, 0, A.data_ptr(), B.data_ptr(), C.data_ptr(), bv.data_ptr() if bias else 0, buf, len(buf))
-        _lib.prof_enable(1)
-        if entry == "rowsum":
-            call("srk_gemm_rowsum_f32", ta, tb, M, N, K, 0.5, ptr(A), ac, ptr(B), bc, beta, ptr(C), N, ptr(rs), stream_ptr())
-        elif entry == "g16b":
-            call("srk_gemm_16_batched", ta, tb, M, N, K, 0.5, ptr(A), ac, sA, ptr(B), bc, sB, beta, ptr(C), N, sC, batch,
-                 stream_ptr())
-        else:
-            call("srk_gemm_16" if o16 else "srk_gemm_f32", ta, tb, M, N, K, 0.5, ptr(A), ac, ptr(B), bc, beta, ptr(C), N,
-                 ptr(bv) if bias else None, bias, stream_ptr())
-        torch.cuda.synchronize()
-        ran = [(k["name"], k["kernel"], k["launches"]) for k in _lib.prof_kernels()]
+        with _lib.options(**opts):
+            call("srk_gemm_plan_describe", ta, tb, M, N, K, ac, bc, N, batch, sA, sB, sC, bias, int(entry == "rowsum"),
+                 int(o16), -1, 0, 0, A.data_ptr(), B.data_ptr(), C.data_ptr(), bv.data_ptr() if bias else 0, buf, len(buf))
+            _lib.prof_enable(1)
+            if entry == "rowsum":
+                call("srk_gemm_rowsum_f32", ta, tb, M, N, K, 0.5, ptr(A), ac, ptr(B), bc, beta, ptr(C), N, ptr(rs), stream_ptr())
+            elif entry == "g16b":
+                call("srk_gemm_16_batched", ta, tb, M, N, K, 0.5, ptr(A), ac, sA, ptr(B), bc, sB, beta, ptr(C), N, sC, batch,
+                     stream_ptr())
+            else:
+                call("srk_gemm_16" if o16 else "srk_gemm_f32", ta, tb, M, N, K, 0.5, ptr(A), ac, ptr(B), bc, beta, ptr(C), N,
+                     ptr(bv) if bias else None, bias, stream_ptr())
+            torch.cuda.synchronize()
+            ran = [(k["name"], k["kernel"], k["launches"]) for k in _lib.prof_kernels()]
     finally:
         _lib.prof_enable(0)
-        for k in opts:
-            _lib.set_option(k, 1 if k == "gemm_skinny" else 0)
         _lib.set_matmul_precision("fp32")
     name, detail = buf.value.decode().split("\n")[0].split("|")
     assert ran == [(name, detail, 1)]

@@ -157,12 +157,9 @@ def test_mfcc_variants_bitwise(gpu, layout):
     x, _ = synthetic_clips(1100, seed=21)
     xd = torch.from_numpy(x).cuda()
     outs = []
-    try:
-        for v in (0, 1, 2, 3):
-            _lib.set_option("mfcc_variant", v)
+    for v in (0, 1, 2, 3):
+        with _lib.options(mfcc_variant=v):
             outs.append(K.mfcc(xd, time_major=layout).cpu())
-    finally:
-        _lib.set_option("mfcc_variant", 3)
     for o in outs[1:]:
         assert torch.equal(outs[0], o)
 

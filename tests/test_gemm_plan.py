@@ -32,13 +32,8 @@ def describe(a):
 
 @pytest.mark.parametrize("row", TABLE, ids=[r["case"] for r in TABLE])
 def test_plan_names_what_the_parent_launched(row):
-    try:
-        for k, v in row["options"].items():
-            _lib.set_option(k, v)
+    with _lib.options(**row["options"]):
         got, err = describe(row["args"])
-    finally:
-        for k in row["options"]:
-            _lib.set_option(k, {"gemm_skinny": 1, "gemm_streamk": 1}.get(k, 0))
     assert got == row.get("expect")
     assert err == row.get("error")
 
@@ -68,12 +63,9 @@ def test_batched_row_sums_run_on_the_ping_pong_kernel_or_are_refused(ta, tb, ali
     a = dict(ta=ta, tb=tb, M=M, N=N, K=K, lda=ac + (align == "lda+1"), ldb=bc + 2 * (align == "ldb+2"), ldc=N, batch=2,
              sA=ar * (ac + 1) + 2 * (align == "sA+2"), sB=br * (bc + 2), sC=M * N, bias_mode=0, rowsum=1, ops16=0, prec=0,
              no_split=0, plan_batch=0, a_mod16=4 * (align == "a+4"), b_mod16=4 * (align == "b+4"), c_null=0, bias=0)
-    try:
-        _lib.set_option("gemm32_kernel", kernel32)
+    with _lib.options(gemm32_kernel=kernel32):
         got2, err2 = describe(a)
         got1, err1 = describe(dict(a, batch=1, plan_batch=2))
-    finally:
-        _lib.set_option("gemm32_kernel", 0)
     assert (err2 == BATCHED_ROWSUM_ERROR) != (got2 is not None and "|gemm_p32_kernel<" in got2), (got2, err2)
     assert err1 is None
     assert ("|gemm_p32_kernel<" in got1) == (got2 is not None), (got1, got2, err2)

@@ -38,9 +38,7 @@ def test_flag_words_below_census_and_chunk_independent_backward(opts, prec):
 def _check_flag_words(opts, prec, backward):
     # 16-bit with gru_lp_wide: batches over 256 rows run as 512-row launches of 64-row workgroups
     wide = prec != 0 and opts["gru_lp_32x32"] and opts["gru_lp_wide"]
-    try:
-        for k, v in opts.items():
-            _lib.set_option(k, v)
+    with _lib.options(**opts):
         first = _audit(256, prec, backward)
         for B in (1, 63, 64, 200, 256, 300, 512, 1000, 4096):
             mx, n, cen = _audit(B, prec, backward)
@@ -48,10 +46,6 @@ def _check_flag_words(opts, prec, backward):
             assert n == ((B + 511) // 512 if wide and B > 256 else (B + 255) // 256)
             if B % 256 == 0:
                 assert mx == first[0]          # every full chunk touches the same words
-    finally:
-        _lib.set_option("gru_fp32_dual_chain", 1)
-        _lib.set_option("gru_lp_32x32", 1)
-        _lib.set_option("gru_lp_wide", 1)
 
 
 # ------------------------------------------------------------------ workspace layout (csrc/gru.hip, struct GruWs)

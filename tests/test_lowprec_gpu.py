@@ -308,20 +308,18 @@ def test_conv_16bit_sources_bit_identical(prec, shape):
     gy = torch.randn(N, Ho, Wo, Co, generator=g).cuda()
     outs = []
     try:
-        _lib.set_option("conv_ring", 6)   # the register-staged 16-bit kernels on both sides (no 16-bit ring)
+        # conv_ring = 6: the register-staged 16-bit kernels on both sides (no 16-bit ring)
         for on in (0, 1):
-            _lib.set_option("conv16_sources", on)
-            xm, wm, bm = (t.clone().requires_grad_(True) for t in (x, w, b))
-            _lib.prof_enable(1)
-            ym = snn._Conv2dNHWCFn.apply(xm, wm, bm, (ph, pw), (sh, sw))
-            (ym * gy).sum().backward()
-            torch.cuda.synchronize()
-            assert (_lib.prof_read("conv_to16")[0] > 0) == bool(on)
-            _lib.prof_enable(0)
-            outs.append((ym.detach(), xm.grad, wm.grad, bm.grad))
+            with _lib.options(conv_ring=6, conv16_sources=on):
+                xm, wm, bm = (t.clone().requires_grad_(True) for t in (x, w, b))
+                _lib.prof_enable(1)
+                ym = snn._Conv2dNHWCFn.apply(xm, wm, bm, (ph, pw), (sh, sw))
+                (ym * gy).sum().backward()
+                torch.cuda.synchronize()
+                assert (_lib.prof_read("conv_to16")[0] > 0) == bool(on)
+                _lib.prof_enable(0)
+                outs.append((ym.detach(), xm.grad, wm.grad, bm.grad))
     finally:
-        _lib.set_option("conv16_sources", 1)
-        _lib.set_option("conv_ring", 0x77)
         _lib.prof_enable(0)
     for a, c in zip(outs[0][:3], outs[1][:3]):
         assert torch.equal(a, c)
@@ -408,13 +406,10 @@ def test_gemm_16bit_kernels_at_tile_edges(prec, kernel, ta, tb, M, N, K):
     opB = (B.T if tb else B).double()
     ref = opA @ opB + C0.double()
     Ad, Bd, Cd = A.cuda(), B.cuda(), C0.clone().cuda()
-    _lib.set_option("gemm16_kernel", kernel)
-    try:
+    with _lib.options(gemm16_kernel=kernel):
         call("srk_gemm_16", ta, tb, M, N, K, 1.0, ptr(Ad), Ad.shape[1], ptr(Bd), Bd.shape[1], 1.0, ptr(Cd), N,
              None, 0, stream_ptr())
         torch.cuda.synchronize()
-    finally:
-        _lib.set_option("gemm16_kernel", 0)
     scale = (opA.abs() @ opB.abs()).max().item()
     assert (Cd.cpu().double() - ref).abs().max().item() <= 2e-6 * (1 + scale)
 
@@ -470,14 +465,11 @@ def _batched_dwhh_case(snn):
     w = torch.randn(B, T, 2 * H, device="cuda")
     grads = []
     for batched in (1, 0):
-        _lib.set_option("gru_dwhh_batched", batched)
-        try:
+        with _lib.options(gru_dwhh_batched=batched):
             for p in mine.parameters():
                 p.grad = None
             (mine(x)[0] * w).sum().backward()
             torch.cuda.synchronize()
-        finally:
-            _lib.set_option("gru_dwhh_batched", 1)
         grads.append({n: p.grad.detach().clone() for n, p in mine.named_parameters()})
     for n in grads[0]:
         a, b = grads[0][n], grads[1][n]
@@ -511,19 +503,14 @@ def test_bigru_backward_when_batched_dwhh_is_unavailable(gpu, precision, H, opts
     grads = []
     try:
         _lib.set_matmul_precision(precision)
-        for k, v in opts.items():
-            _lib.set_option(k, v)
         for batched in (1, 0):
-            _lib.set_option("gru_dwhh_batched", batched)
-            mine = snn.BiGRU(IN, H, num_layers=L).cuda()
-            mine.load_state_dict(ref.state_dict())
-            (mine(x)[0] * w).sum().backward()
-            torch.cuda.synchronize()
-            grads.append({n: p.grad.detach().clone() for n, p in mine.named_parameters()})
+            with _lib.options(gru_dwhh_batched=batched, **opts):
+                mine = snn.BiGRU(IN, H, num_layers=L).cuda()
+                mine.load_state_dict(ref.state_dict())
+                (mine(x)[0] * w).sum().backward()
+                torch.cuda.synchronize()
+                grads.append({n: p.grad.detach().clone() for n, p in mine.named_parameters()})
     finally:
-        _lib.set_option("gru_dwhh_batched", 1)
-        _lib.set_option("gru_persistent", 1)
-        _lib.set_option("gemm32_kernel", 0)
         _lib.set_matmul_precision("fp32")
     for n in grads[0]:
         assert torch.isfinite(grads[0][n]).all(), n
@@ -547,15 +534,12 @@ def test_gemm16_pingpong(prec, ta, tb, M, N, K, beta):
     ref = 0.5 * (opA @ opB) + beta * C0.double()
     Ad, Bd = A.cuda(), B.cuda()
     outs = []
-    try:
-        for kern in (2, 1):
-            _lib.set_option("gemm16_kernel", kern)
+    for kern in (2, 1):
+        with _lib.options(gemm16_kernel=kern):
             Cd = C0.clone().cuda()
             call("srk_gemm_16", ta, tb, M, N, K, 0.5, ptr(Ad), Ad.shape[1], ptr(Bd), Bd.shape[1], beta, ptr(Cd), N,
                  None, 0, stream_ptr())
             outs.append(Cd.cpu().double())
-    finally:
-        _lib.set_option("gemm16_kernel", 0)
     scale = (opA.abs() @ opB.abs()).max().item()
     assert (outs[0] - ref).abs().max().item() <= 2e-6 * (1 + scale)
     assert (outs[0] - outs[1]).abs().max().item() <= 2e-6 * (1 + scale)
@@ -579,20 +563,15 @@ def test_conv_16bit_ring(prec, shape):
     Ho, Wo = (H + 2 * ph - KH) // sh + 1, (W + 2 * pw - KW) // sw + 1
     gy = torch.randn(N, Ho, Wo, Co, generator=g).cuda()
     outs = []
-    try:
-        # ring (one k-step per MFMA section), ring with whole K-tiles per section (conv_ring_qs, every width),
-        # register-staged
-        for mask, qs in ((0x70 | 6, 0), (0x70 | 6, 7), (6, 0)):
-            _lib.set_option("conv_ring", mask)
-            _lib.set_option("conv_ring_qs", qs)
+    # ring (one k-step per MFMA section), ring with whole K-tiles per section (conv_ring_qs, every width),
+    # register-staged
+    for mask, qs in ((0x70 | 6, 0), (0x70 | 6, 7), (6, 0)):
+        with _lib.options(conv_ring=mask, conv_ring_qs=qs):
             xm, wm, bm = (t.clone().requires_grad_(True) for t in (x, w, b))
             ym = snn._Conv2dNHWCFn.apply(xm, wm, bm, (ph, pw), (sh, sw))
             (ym * gy).sum().backward()
             torch.cuda.synchronize()
             outs.append([t.detach().double() for t in (ym, xm.grad, wm.grad, bm.grad)])
-    finally:
-        _lib.set_option("conv_ring", 0x77)
-        _lib.set_option("conv_ring_qs", 6)
     for a, c in zip(outs[0], outs[1]):
         assert torch.equal(a, c)   # the same MFMA order per accumulator
     for a, c in zip(outs[0], outs[2]):
@@ -617,25 +596,22 @@ def test_bigru_dwhh_fused_matches_gemm(prec, B, T, IN, wide):
     res = []
     try:
         _lib.set_matmul_precision(prec)
-        _lib.set_option("gru_lp_wide", wide)
         for fused in (1, 0, 3, 5, 7):   # 3 / 5 / 7: the h_prev fetch / priority timing variants, bitwise mode 1
-            _lib.set_option("gru_dwhh_fused", fused)
-            mine.zero_grad()
-            xm = x.clone().requires_grad_(True)
-            _lib.prof_enable(True)
-            ym, _ = mine(xm)
-            (ym * w).sum().backward()
-            torch.cuda.synchronize()
-            kinds = [k["kernel"] for k in _lib.prof_kernels()]
-            _lib.prof_enable(False)
-            if fused:   # the fused kernel ran and no dW_hh GEMM did
-                assert any("_lp2dw" in k for k in kinds), kinds
-                assert not any("1536x512" in k for k in kinds), kinds
-            res.append({"y": ym.detach().clone(), "dx": xm.grad.clone(),
-                        **{n: p.grad.detach().clone() for n, p in mine.named_parameters()}})
+            with _lib.options(gru_lp_wide=wide, gru_dwhh_fused=fused):
+                mine.zero_grad()
+                xm = x.clone().requires_grad_(True)
+                _lib.prof_enable(True)
+                ym, _ = mine(xm)
+                (ym * w).sum().backward()
+                torch.cuda.synchronize()
+                kinds = [k["kernel"] for k in _lib.prof_kernels()]
+                _lib.prof_enable(False)
+                if fused:   # the fused kernel ran and no dW_hh GEMM did
+                    assert any("_lp2dw" in k for k in kinds), kinds
+                    assert not any("1536x512" in k for k in kinds), kinds
+                res.append({"y": ym.detach().clone(), "dx": xm.grad.clone(),
+                            **{n: p.grad.detach().clone() for n, p in mine.named_parameters()}})
     finally:
-        _lib.set_option("gru_dwhh_fused", 1)
-        _lib.set_option("gru_lp_wide", 1)
         _lib.set_matmul_precision("fp32")
     assert _lib.spin_timeouts() == 0
     for v in res[2:]:
@@ -676,20 +652,19 @@ def test_bigru_fwd_worker(prec, B, T, IN):
     try:
         _lib.set_matmul_precision(prec)
         for ow in (1, 1, 0):
-            _lib.set_option("gru_fwd_worker", ow)
-            mine.zero_grad()
-            xm = x.clone().requires_grad_(True)
-            _lib.prof_enable(True)
-            ym, _ = mine(xm)
-            (ym * w).sum().backward()
-            torch.cuda.synchronize()
-            kinds = [k["kernel"] for k in _lib.prof_kernels()]
-            _lib.prof_enable(False)
-            assert any("_lp2ow" in k for k in kinds) == bool(ow), kinds
-            res.append({"y": ym.detach().clone(), "dx": xm.grad.clone(),
-                        **{n: p.grad.detach().clone() for n, p in mine.named_parameters()}})
+            with _lib.options(gru_fwd_worker=ow):
+                mine.zero_grad()
+                xm = x.clone().requires_grad_(True)
+                _lib.prof_enable(True)
+                ym, _ = mine(xm)
+                (ym * w).sum().backward()
+                torch.cuda.synchronize()
+                kinds = [k["kernel"] for k in _lib.prof_kernels()]
+                _lib.prof_enable(False)
+                assert any("_lp2ow" in k for k in kinds) == bool(ow), kinds
+                res.append({"y": ym.detach().clone(), "dx": xm.grad.clone(),
+                            **{n: p.grad.detach().clone() for n, p in mine.named_parameters()}})
     finally:
-        _lib.set_option("gru_fwd_worker", 0)
         _lib.set_matmul_precision("fp32")
     assert _lib.spin_timeouts() == 0
     a, a2, c = res
@@ -726,10 +701,8 @@ def test_conv_fast16_gathers_bitwise(prec, shape, pooled):
     b = torch.randn(Co, generator=g).cuda()
     gy = torch.randn(N, Ho, Wo // 4 if pooled else Wo, Co, generator=g).cuda()
     outs = []
-    try:
-        _lib.set_option("conv_ring", 6)
-        for fast in (1, 0):
-            _lib.set_option("conv_fast16", fast)
+    for fast in (1, 0):
+        with _lib.options(conv_ring=6, conv_fast16=fast):
             xm, wm, bm = (t.clone().requires_grad_(True) for t in (x, w, b))
             if pooled:
                 ym = snn._ConvPoolNHWCFn.apply(xm, wm, bm, (ph, pw), 4)
@@ -738,9 +711,6 @@ def test_conv_fast16_gathers_bitwise(prec, shape, pooled):
             (ym * gy).sum().backward()
             torch.cuda.synchronize()
             outs.append((ym.detach(), xm.grad, wm.grad, bm.grad))
-    finally:
-        _lib.set_option("conv_fast16", 1)
-        _lib.set_option("conv_ring", 0x77)
     for a, c in zip(*outs):
         assert torch.isfinite(a).all()
         assert torch.equal(a, c)
@@ -764,16 +734,15 @@ def test_conv_row16_equals_gemm(prec, N, form):
     outs = []
     try:
         for row in (form, 0):
-            _lib.set_option("conv_row16", row)
-            _lib.prof_enable(True)
-            with torch.no_grad():
-                y = snn._ConvPoolNHWCFn.apply(x, w, b, (0, 3), 4)
-            torch.cuda.synchronize()
-            used = any("conv_row16" in e["kernel"] for e in _lib.prof_kernels())
-            _lib.prof_enable(False)
-            outs.append((y, used))
+            with _lib.options(conv_row16=row):
+                _lib.prof_enable(True)
+                with torch.no_grad():
+                    y = snn._ConvPoolNHWCFn.apply(x, w, b, (0, 3), 4)
+                torch.cuda.synchronize()
+                used = any("conv_row16" in e["kernel"] for e in _lib.prof_kernels())
+                _lib.prof_enable(False)
+                outs.append((y, used))
     finally:
-        _lib.set_option("conv_row16", 1)
         _lib.prof_enable(False)
     (y1, u1), (y0, u0) = outs
     assert u1 and not u0
@@ -789,23 +758,20 @@ def test_conv_row16_equals_gemm(prec, N, form):
     grads, dense = [], []
     try:
         for row in (form, 0):
-            _lib.set_option("conv_row16", row)
-            _lib.set_option("conv_row16_dgrad", form if row else 0)
-            _lib.prof_enable(True)
-            xm, wm, bm = (t.clone().requires_grad_(True) for t in (x, w, b))
-            (snn._ConvPoolNHWCFn.apply(xm, wm, bm, (0, 3), 4) * gy).sum().backward()
-            torch.cuda.synchronize()
-            ks = [e["kernel"] for e in _lib.prof_kernels()]
-            grads.append((xm.grad, wm.grad, bm.grad, any("conv_row16_dgrad" in k for k in ks),
-                          any("conv_row16_wgrad" in k for k in ks)))
-            _lib.prof_enable(False)
-            xm, wm, bm = (t.clone().requires_grad_(True) for t in (x, w, b))
-            (snn._Conv2dNHWCFn.apply(xm, wm, bm, (0, 3), (1, 1)) * gd).sum().backward()
-            torch.cuda.synchronize()
-            dense.append((xm.grad, wm.grad, bm.grad))
+            with _lib.options(conv_row16=row, conv_row16_dgrad=form if row else 0):
+                _lib.prof_enable(True)
+                xm, wm, bm = (t.clone().requires_grad_(True) for t in (x, w, b))
+                (snn._ConvPoolNHWCFn.apply(xm, wm, bm, (0, 3), 4) * gy).sum().backward()
+                torch.cuda.synchronize()
+                ks = [e["kernel"] for e in _lib.prof_kernels()]
+                grads.append((xm.grad, wm.grad, bm.grad, any("conv_row16_dgrad" in k for k in ks),
+                              any("conv_row16_wgrad" in k for k in ks)))
+                _lib.prof_enable(False)
+                xm, wm, bm = (t.clone().requires_grad_(True) for t in (x, w, b))
+                (snn._Conv2dNHWCFn.apply(xm, wm, bm, (0, 3), (1, 1)) * gd).sum().backward()
+                torch.cuda.synchronize()
+                dense.append((xm.grad, wm.grad, bm.grad))
     finally:
-        _lib.set_option("conv_row16", 1)
-        _lib.set_option("conv_row16_dgrad", 2)
         _lib.prof_enable(False)
     assert grads[0][3] and not grads[1][3] and grads[0][4] and not grads[1][4]
     # the data gradient and the dense-dY conv's gradients bitwise; the pooled conv's weight and bias gradients on

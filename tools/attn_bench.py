@@ -80,28 +80,26 @@ def pool_variants(B, T, D):
 
 def bench_pool(B, T, D, rounds, iters):
     variants, keep = pool_variants(B, T, D)
-    try:
-        for v, (fwd, bwd) in variants.items():
-            _lib.set_option("attn_pool_regs", 0 if v == "fused_2pass" else 1)
+    regs = lambda v: _lib.options(attn_pool_regs=0 if v == "fused_2pass" else 1)   # noqa: E731
+    for v, (fwd, bwd) in variants.items():
+        with regs(v):
             for _ in range(3):
                 fwd()
                 bwd()
-        torch.cuda.synchronize()
-        _lib.set_option("attn_pool_regs", 1)
-        # the fused forward against the torch-composed one, on the timed tensors
+    torch.cuda.synchronize()
+    # the fused forward against the torch-composed one, on the timed tensors
+    with regs("fused"):
         variants["fused"][0]()
-        variants["torch"][0]()
-        torch.cuda.synchronize()
-        ref = keep[3]["ctx"].detach()
-        agree = float((keep[0] - ref).abs().max() / ref.abs().max())
-        samples = {(v, d): [] for v in variants for d in ("fwd", "bwd")}
-        for _ in range(rounds):
-            for v, (fwd, bwd) in variants.items():
-                _lib.set_option("attn_pool_regs", 0 if v == "fused_2pass" else 1)   # (between timed windows)
+    variants["torch"][0]()
+    torch.cuda.synchronize()
+    ref = keep[3]["ctx"].detach()
+    agree = float((keep[0] - ref).abs().max() / ref.abs().max())
+    samples = {(v, d): [] for v in variants for d in ("fwd", "bwd")}
+    for _ in range(rounds):
+        for v, (fwd, bwd) in variants.items():
+            with regs(v):   # (between timed windows)
                 samples[v, "fwd"].append(time_calls(fwd, iters))
                 samples[v, "bwd"].append(time_calls(bwd, iters))
-    finally:
-        _lib.set_option("attn_pool_regs", 1)
     nbytes = {"fwd": 4.0 * (B * T * D + 2 * B * D + B * T), "bwd": 4.0 * (2 * B * T * D + 3 * B * D + B * T)}
     res = {"shape": [B, T, D], "bytes_fwd": nbytes["fwd"], "bytes_bwd": nbytes["bwd"],
            "fused_vs_torch_ctx_rel_err": agree}

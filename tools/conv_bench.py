@@ -45,27 +45,26 @@ def run_shape(name, prec, opts):
     b = torch.zeros(Co, device="cuda", requires_grad=True)
     pooled = name == "fb_conv2"
     _lib.set_matmul_precision(prec)
-    for k, v in opts:
-        _lib.set_option(k, v)
     try:
-        r = {}
-        for it in range(3 + MEAS):
-            if it == 3:
-                _lib.prof_enable(True)
-            if pooled:
-                y = snn._ConvPoolNHWCFn.apply(x, w, b, (ph, pw), 4)
-            else:
-                y = snn._Conv2dNHWCFn.apply(x, w, b, (ph, pw), (sh, sw))
-            y.backward(torch.ones_like(y))
-        torch.cuda.synchronize()
-        for k in CATS:
-            c, ms, work = _lib.prof_read(k)
-            if c:
-                unit = "GB/s" if k in ("conv_to16", "conv_colsum") else "TF"
-                r[k] = {"us": round(ms * 1e3 / MEAS, 1), unit: round(work / (ms * 1e-3) / (1e9 if unit == "GB/s" else 1e12), 1)}
-        r["kernels"] = [{"kernel": e["kernel"], "us": round(e["ms_total"] * 1e3 / MEAS, 1)} for e in _lib.prof_kernels()]
-        _lib.prof_enable(False)
-        return r
+        with _lib.options(**dict(opts)):
+            r = {}
+            for it in range(3 + MEAS):
+                if it == 3:
+                    _lib.prof_enable(True)
+                if pooled:
+                    y = snn._ConvPoolNHWCFn.apply(x, w, b, (ph, pw), 4)
+                else:
+                    y = snn._Conv2dNHWCFn.apply(x, w, b, (ph, pw), (sh, sw))
+                y.backward(torch.ones_like(y))
+            torch.cuda.synchronize()
+            for k in CATS:
+                c, ms, work = _lib.prof_read(k)
+                if c:
+                    unit = "GB/s" if k in ("conv_to16", "conv_colsum") else "TF"
+                    r[k] = {"us": round(ms * 1e3 / MEAS, 1), unit: round(work / (ms * 1e-3) / (1e9 if unit == "GB/s" else 1e12), 1)}
+            r["kernels"] = [{"kernel": e["kernel"], "us": round(e["ms_total"] * 1e3 / MEAS, 1)} for e in _lib.prof_kernels()]
+            _lib.prof_enable(False)
+            return r
     finally:
         _lib.set_matmul_precision("fp32")
 

@@ -29,8 +29,11 @@ VARIANTS = {"dc": {"gru_fp32_dual_chain": 1, "gru_dc_offset_ns": 0, "gru_fp32_fa
 
 
 def run(B, T, IN, reps, opts):
-    for k, v in opts.items():
-        _lib.set_option(k, v)
+    with _lib.options(**opts):
+        return _run(B, T, IN, reps)
+
+
+def _run(B, T, IN, reps):
     torch.manual_seed(0)
     m = snn.BiGRU(IN, 512, num_layers=1).cuda()
     x = torch.randn(B, T, IN, device="cuda", requires_grad=True)
@@ -64,8 +67,6 @@ def main():
     for name in a.variants.split(","):
         for IN in (39, 1024):
             print(name, "IN=%d" % IN, json.dumps(run(a.B, a.T, IN, a.reps, dict(DEFAULTS, **VARIANTS[name]))), flush=True)
-    for k, v in DEFAULTS.items():
-        _lib.set_option(k, v)
 
 
 if __name__ == "__main__":

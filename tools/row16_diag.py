@@ -21,20 +21,18 @@ dyp = torch.randn(N, H, W // 4, Co, generator=g).cuda()
 _lib.set_matmul_precision("bf16")
 res = {}
 for row in (1, 0):
-    _lib.set_option("conv_row16", row)
-    _lib.set_option("conv_row16_dgrad", row)
-    y = torch.empty(N, H, W // 4, Co, device="cuda")
-    arg = torch.empty(N, H, W // 4, Co, dtype=torch.uint8, device="cuda")
-    ws = torch.empty(int(_lib.lib().srk_conv2d_workspace_floats(Ci, Co, 1, 7)), device="cuda")
-    wr = ctypes.c_int(0)
-    call("srk_conv2d_nhwc_fwd_pool", ptr(x), N, H, W, Ci, ptr(w), ptr(b), Co, 1, 7, 0, 3, 4, ptr(y), ptr(arg), ptr(ws),
-         None, ctypes.byref(wr), stream_ptr())
-    dx, dw, db = torch.empty_like(x), torch.empty_like(w), torch.empty(Co, device="cuda")
-    call("srk_conv2d_nhwc_bwd_pool", ptr(x), N, H, W, Ci, ptr(w), Co, 1, 7, 0, 3, 4, ptr(dyp), ptr(arg), ptr(dx), ptr(dw),
-         ptr(db), ptr(ws), None, stream_ptr())
-    torch.cuda.synchronize()
-    res[row] = (y, arg, dx, dw, db)
-_lib.set_option("conv_row16", 1)
+    with _lib.options(conv_row16=row, conv_row16_dgrad=row):
+        y = torch.empty(N, H, W // 4, Co, device="cuda")
+        arg = torch.empty(N, H, W // 4, Co, dtype=torch.uint8, device="cuda")
+        ws = torch.empty(int(_lib.lib().srk_conv2d_workspace_floats(Ci, Co, 1, 7)), device="cuda")
+        wr = ctypes.c_int(0)
+        call("srk_conv2d_nhwc_fwd_pool", ptr(x), N, H, W, Ci, ptr(w), ptr(b), Co, 1, 7, 0, 3, 4, ptr(y), ptr(arg), ptr(ws),
+             None, ctypes.byref(wr), stream_ptr())
+        dx, dw, db = torch.empty_like(x), torch.empty_like(w), torch.empty(Co, device="cuda")
+        call("srk_conv2d_nhwc_bwd_pool", ptr(x), N, H, W, Ci, ptr(w), Co, 1, 7, 0, 3, 4, ptr(dyp), ptr(arg), ptr(dx), ptr(dw),
+             ptr(db), ptr(ws), None, stream_ptr())
+        torch.cuda.synchronize()
+        res[row] = (y, arg, dx, dw, db)
 for name, a, c in zip(("y", "arg", "dx", "dw", "db"), res[1], res[0]):
     d = (a.double() - c.double()).abs()
     bad = (d > 0).nonzero()
@@ -49,15 +47,13 @@ print("wrong fraction by image row (first 16):", [round(v, 2) for v in bad.float
 dyd = torch.randn(N, H, W, Co, generator=g).cuda()
 res2 = {}
 for row in (1, 0):
-    _lib.set_option("conv_row16", row)
-    _lib.set_option("conv_row16_dgrad", row)
-    ws = torch.empty(int(_lib.lib().srk_conv2d_workspace_floats(Ci, Co, 1, 7)), device="cuda")
-    dx, dw = torch.empty_like(x), torch.empty_like(w)
-    call("srk_conv2d_nhwc_bwd", ptr(x), N, H, W, Ci, ptr(w), Co, 1, 7, 0, 3, 1, 1, ptr(dyd), ptr(dx), ptr(dw), None,
-         ptr(ws), stream_ptr())
-    torch.cuda.synchronize()
-    res2[row] = (dx, dw)
-_lib.set_option("conv_row16", 1)
+    with _lib.options(conv_row16=row, conv_row16_dgrad=row):
+        ws = torch.empty(int(_lib.lib().srk_conv2d_workspace_floats(Ci, Co, 1, 7)), device="cuda")
+        dx, dw = torch.empty_like(x), torch.empty_like(w)
+        call("srk_conv2d_nhwc_bwd", ptr(x), N, H, W, Ci, ptr(w), Co, 1, 7, 0, 3, 1, 1, ptr(dyd), ptr(dx), ptr(dw), None,
+             ptr(ws), stream_ptr())
+        torch.cuda.synchronize()
+        res2[row] = (dx, dw)
 for name, a, c in zip(("dense dx", "dense dw"), res2[1], res2[0]):
     d = (a.double() - c.double()).abs()
     print(name, "equal" if torch.equal(a, c) else "DIFF max %.3g at %d elems" % (d.max().item(), int((d > 0).sum())))
