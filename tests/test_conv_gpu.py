@@ -25,6 +25,10 @@ CONV2D = [  # N, H, W, Ci, Co, KH, KW, ph, pw   (model_fbanks_cnn.py:72-75 + odd
     (2, 9, 11, 5, 7, 3, 2, 1, 0),
     (24, 98, 40, 64, 128, 1, 7, 0, 3),   # many tiles + deep split-K weight gradient
     (4, 17, 13, 12, 36, 3, 3, 1, 1),     # N % 4 == 0 but odd tile edges
+    # ... ph, pw, sh, sw: a stride along H (with padding: the strided data gradient)
+    (4, 17, 13, 12, 36, 3, 3, 1, 1, 2, 2),
+    (2, 9, 11, 5, 7, 3, 2, 1, 0, 2, 3),
+    (2, 10, 14, 8, 24, 3, 3, 1, 1, 2, 1),
 ]
 
 

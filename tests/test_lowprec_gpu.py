@@ -239,6 +239,9 @@ CONV_LP = [  # N, H, W, Ci, Co, KH, KW, ph, pw, sh, sw  (fbanks_cnn layers, resn
     (4, 17, 13, 12, 36, 3, 3, 1, 1, 1, 1),
     (2, 1, 1000, 64, 128, 1, 15, 0, 7, 1, 2),
     (2, 1, 16000, 1, 64, 1, 80, 0, 38, 1, 16),
+    (4, 17, 13, 12, 36, 3, 3, 1, 1, 2, 2),      # a stride along H (with padding: the strided data gradient)
+    (2, 9, 11, 5, 7, 3, 2, 1, 0, 2, 3),
+    (2, 10, 14, 8, 24, 3, 3, 1, 1, 2, 1),
 ]
 
 
@@ -287,6 +290,7 @@ CONV_S16 = [  # 8-aligned channel counts: the pre-rounded 16-bit source path (op
     (3, 1, 125, 512, 512, 1, 15, 0, 7, 1, 1),
     (2, 5, 7, 8, 24, 3, 3, 1, 1, 1, 1),         # partial 64-row / -column tiles
     (2, 1, 500, 128, 256, 1, 1, 0, 0, 1, 2),    # 1x1 downsample
+    (2, 10, 14, 8, 24, 3, 3, 1, 1, 2, 1),       # a stride along H
 ]
 
 
@@ -683,7 +687,8 @@ def test_bigru_fwd_worker(prec, B, T, IN):
         assert err <= 2e-3, (n, err)
 
 
-@pytest.mark.parametrize("shape", CONV_S16 + [(3, 17, 24, 128, 64, 3, 3, 1, 1, 1, 1), (5, 98, 40, 64, 128, 1, 7, 0, 3, 1, 1)])
+# (the stride-1 rows of CONV_S16 and two more; its strided-H row, which the fused pool does not take, runs below)
+@pytest.mark.parametrize("shape", CONV_S16[:7] + [(3, 17, 24, 128, 64, 3, 3, 1, 1, 1, 1), (5, 98, 40, 64, 128, 1, 7, 0, 3, 1, 1)])
 @pytest.mark.parametrize("pooled", [False, True])
 def test_conv_fast16_gathers_bitwise(prec, shape, pooled):
     """Option conv_fast16: the register-staged 16-bit-source convs gathering one uniform tap per K-tile
@@ -714,6 +719,12 @@ def test_conv_fast16_gathers_bitwise(prec, shape, pooled):
     for a, c in zip(*outs):
         assert torch.isfinite(a).all()
         assert torch.equal(a, c)
+
+
+@pytest.mark.parametrize("shape", CONV_S16[7:])
+def test_conv_fast16_gathers_bitwise_strided_h(prec, shape):
+    """The same comparison on the rows of CONV_S16 with a stride along H (unpooled: the fused pool needs stride 1)."""
+    test_conv_fast16_gathers_bitwise(prec, shape, False)
 
 
 @pytest.mark.parametrize("N", [3, 32])
