@@ -253,6 +253,17 @@ int srk_gemm_plan_describe(int trans_a, int trans_b, int64_t M, int64_t N, int64
                            int64_t ldc, int batch, int64_t sA, int64_t sB, int64_t sC, int bias_mode, int has_rowsum,
                            int operands16, int prec, int no_split, int plan_batch, uint64_t a_addr, uint64_t b_addr,
                            uint64_t c_addr, uint64_t bias_addr, char* buf, int64_t cap);
+/* Host only, no GPU needed: the zero-block packing plan of a K dimension whose operand rows are zero but for
+ * `count` live rows first, first + stride, ... (stride >= 8, all below K).  K is walked in slabs of `slab` k (a
+ * positive multiple of 16, the K split of the GEMM being packed); every 8-aligned k block holding a live row is
+ * kept in the slab of its original k, and every slab is padded with zero blocks to *packed_slab, the longest
+ * slab's kept length rounded up to 16.  blocks receives the kept block indices (k / 8) slab by slab in k order
+ * (`count` of them; blocks_cap >= count), slab_counts[s] the number kept in slab s (slabs_cap >= *n_slabs =
+ * ceil(K / slab)).  The last-step top BiGRU layer packs its reverse direction's dW_ih GEMM by this plan.
+ * SRK_ERR_INVALID on arguments outside those ranges.                                               */
+int srk_gemm_pack_plan(int64_t K, int64_t slab, int64_t first, int64_t stride, int64_t count, int64_t* blocks,
+                       int64_t blocks_cap, int64_t* slab_counts, int64_t slabs_cap, int64_t* n_slabs,
+                       int64_t* packed_slab);
 
 /* ---------------------------------------------------------------- K5: bidirectional GRU layer
  * nn.GRU(in, H, bidirectional=True, batch_first=True), one layer, PyTorch gate order [r; z; n],

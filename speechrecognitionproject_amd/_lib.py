@@ -68,6 +68,8 @@ _SIGS = {
     "srk_gemm_plan_describe": [_I, _I, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I64, _I64, _I64, _I, _I, _I, _I, _I, _I,
                                ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p,
                                _I64],
+    "srk_gemm_pack_plan": [_I64, _I64, _I64, _I64, _I64, ctypes.POINTER(_I64), _I64, ctypes.POINTER(_I64), _I64,
+                           ctypes.POINTER(_I64), ctypes.POINTER(_I64)],
     "srk_gru_workspace_floats": [_I64, _I64, _I64, _I64, _I],
     "srk_gru_layer_fwd": [_P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P],
     "srk_gru_layer_bwd": [_P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
@@ -218,6 +220,22 @@ def prof_kernels():
         out.append({"name": name, "kernel": detail or name, "launches": int(n), "ms_total": float(ms),
                     "work": float(work), "bytes": float(nbytes)})
     return out
+
+
+def gemm_pack_plan(K, slab, first, stride, count):
+    """srk_gemm_pack_plan: ([kept 8-deep k block indices of slab s, ...] per slab, packed slab length)."""
+    n = max(int(count), 0)
+    ns = max(-(-int(K) // int(slab)), 0) if slab > 0 else 0
+    blocks = (_I64 * max(n, 1))()
+    counts = (_I64 * max(ns, 1))()
+    n_slabs, pslab = _I64(0), _I64(0)
+    call("srk_gemm_pack_plan", K, slab, first, stride, count, blocks, n, counts, ns, ctypes.byref(n_slabs),
+         ctypes.byref(pslab))
+    out, at = [], 0
+    for s in range(n_slabs.value):
+        out.append([int(b) for b in blocks[at:at + counts[s]]])
+        at += counts[s]
+    return out, int(pslab.value)
 
 
 def scratch_generation():

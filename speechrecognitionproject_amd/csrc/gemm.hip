@@ -1347,8 +1347,10 @@ struct P32Half {
   __device__ static __forceinline__ int64_t kstep_bytes(int64_t ld) { return KC ? 4 : 4 * ld; }
 };
 
+// The kernel's body for block `blk` of ka's grid and batch entry z: gemm_p32_kernel runs it with its own block
+// index, gemm_p32_group_kernel with the index inside the member it picked.
 template <bool TA, bool TB>
-__global__ __launch_bounds__(512, 1) void gemm_p32_kernel(KernelArgs ka) {
+__device__ __forceinline__ void gemm_p32_body(const KernelArgs& ka, const int blk, const int64_t z) {
   constexpr int BK = kP32BK, NST = 4;
   constexpr bool AKC = !TA, BKC = TB;
   using HA = P32Half<AKC>;
@@ -1369,9 +1371,9 @@ __global__ __launch_bounds__(512, 1) void gemm_p32_kernel(KernelArgs ka) {
   int64_t sk_it = 0, sk_end = 0;
   const int64_t sk_total = (int64_t)ka.tiles * ka.sk_ki;
   if (sk) {
-    int lin = blockIdx.x;
+    int lin = blk;
     if (ka.remap) {   // the XCD remap of map_tile: neighbouring runs (tiles) on one XCD
-      const int b = blockIdx.x, xcd = b & 7, q = ka.nblk >> 3, r = ka.nblk & 7;
+      const int b = blk, xcd = b & 7, q = ka.nblk >> 3, r = ka.nblk & 7;
       lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
     }
     sk_it = sk_begin(lin, sk_total, ka.sk_wgs);
@@ -1395,7 +1397,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p32_kernel(KernelArgs ka) {
     if (!first_seg) __syncthreads();   // the previous segment's epilogue is done with the LDS ring
   } else {
     if (!first_seg) break;
-    map_tile(ka.nblk, ka.tiles, ka.tiles_m, ka.tiles_n, ka.group_m, ka.remap != 0, split, tm, tn);
+    map_tile_at(blk, ka.nblk, ka.tiles, ka.tiles_m, ka.tiles_n, ka.group_m, ka.remap != 0, split, tm, tn);
     kb0 = split * ka.kchunk;
     ke = (kb0 + ka.kchunk < d.K) ? kb0 + ka.kchunk : d.K;
   }
@@ -1408,7 +1410,6 @@ __global__ __launch_bounds__(512, 1) void gemm_p32_kernel(KernelArgs ka) {
     return u32x4s{(unsigned)__builtin_amdgcn_readfirstlane((unsigned)a),
                   (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(a >> 32)), 0x7ffffff0u, 0x00020000u};
   };
-  const int64_t z = blockIdx.y;   // batch index (grid.y = batch)
   const u32x4s rsA = rsrc32(d.A + z * d.sA), rsB = rsrc32(d.B + z * d.sB);
   constexpr unsigned kOOB = 0x80000000u;
   unsigned vo[4];
@@ -1518,6 +1519,31 @@ __global__ __launch_bounds__(512, 1) void gemm_p32_kernel(KernelArgs ka) {
     }
   }
   }   // segments
+}
+
+template <bool TA, bool TB>
+__global__ __launch_bounds__(512, 1) void gemm_p32_kernel(KernelArgs ka) {
+  gemm_p32_body<TA, TB>(ka, (int)blockIdx.x, (int64_t)blockIdx.y);   // grid.y = batch
+}
+
+// Up to kGemmGroupMax part-GEMMs in one launch (gemm_f32_group): member i owns blocks [first[i], first[i] + its
+// nblk), first[i] a multiple of 8 so that a member-local block index keeps the workgroup's XCD (map_tile's remap);
+// the blocks between two members' ranges are fillers and return at once.  Members are batch 1 and not stream-K.
+struct GroupArgs {
+  KernelArgs m[kGemmGroupMax];
+  int first[kGemmGroupMax];
+  int n;
+};
+template <bool TA, bool TB>
+__global__ __launch_bounds__(512, 1) void gemm_p32_group_kernel(GroupArgs ga) {
+  const int b = (int)blockIdx.x;
+  int i = 0;
+#pragma unroll
+  for (int j = 1; j < kGemmGroupMax; ++j)
+    if (j < ga.n && b >= ga.first[j]) i = j;
+  const int blk = b - ga.first[i];
+  if (blk >= ga.m[i].nblk) return;
+  gemm_p32_body<TA, TB>(ga.m[i], blk, 0);
 }
 
 // Stream-K fixup: a tile covered by several runs = the sum of its partial slabs in run order, then
@@ -1808,6 +1834,12 @@ int gemm_plan(const GemmDesc& d, GemmPlan& p) {
   const int esz = ops16 ? 2 : 4;
   const double ext_a = (double)(d.ta ? d.K : d.M) * d.lda * esz, ext_b = (double)(d.tb ? d.N : d.K) * d.ldb * esz;
   const int pb = std::max(d.batch, d.plan_batch);   // the batch the plan is made for (GemmDesc::plan_batch)
+  const int64_t PM = d.plan_M > 0 ? d.plan_M : d.M;   // ... and the row count (GemmDesc::plan_M)
+  SRK_REQUIRE(d.plan_M == 0 || d.plan_M >= d.M, SRK_ERR_INVALID, "gemm: plan_M below M");
+  SRK_REQUIRE(d.pin_splits == 0 || (d.pin_splits >= 1 && d.pin_kchunk > 0 && d.batch == 1 && !d.no_split &&
+                                    (int64_t)(d.pin_splits - 1) * d.pin_kchunk < d.K &&
+                                    d.K <= (int64_t)d.pin_splits * d.pin_kchunk),
+              SRK_ERR_INVALID, "gemm: pinned K split does not cover K");
   p.prec = prec;
   p.f16 = prec == kPrecF16;
   p.ext_a = ext_a;
@@ -1822,6 +1854,7 @@ int gemm_plan(const GemmDesc& d, GemmPlan& p) {
   auto tiles_and_split = [&](GemmFamily family, const Variant& v, int BK, bool allow_split, bool split_batched) -> int {
     const int BM = v.bm, BN = v.bn;
     const int64_t tm = (d.M + BM - 1) / BM, tn = (d.N + BN - 1) / BN;
+    const int64_t ptiles = (PM + BM - 1) / BM * tn;   // the output grid the split is chosen for
     SRK_REQUIRE(tm * tn <= (INT32_MAX >> 5) && d.batch <= 65535, SRK_ERR_INVALID, "gemm: grid too large");
     p.family = family;
     p.kernel = v.kernel;
@@ -1840,10 +1873,16 @@ int gemm_plan(const GemmDesc& d, GemmPlan& p) {
     ka.remap = env.remap;
     // Split K when the output grid leaves resident slots idle and K is long (tile::choose_splits).
     const bool can_split = allow_split && !d.no_split && (pb == 1 || split_batched);
-    int splits = can_split ? choose_splits(tm * tn * pb, d.K, BK, slots, 16) : 1;
+    int splits = can_split ? choose_splits(ptiles * pb, d.K, BK, slots, 16) : 1;
     if (env.splits > 0 && d.batch == 1 && d.K >= (int64_t)env.splits * 4 * BK) splits = env.splits;
     ka.kchunk = splits > 1 ? ((d.K + splits - 1) / splits + BK - 1) / BK * BK : std::max<int64_t>(d.K, 1);
     if (splits > 1) splits = (int)((d.K + ka.kchunk - 1) / ka.kchunk);
+    if (d.pin_splits > 0) {   // GemmDesc::pin_splits: the slabs of the GEMM this one is a part (or a packing) of
+      SRK_REQUIRE(d.pin_splits == 1 || d.pin_kchunk % BK == 0, SRK_ERR_INVALID,
+                  "gemm: a pinned K split needs whole K-tiles per slab");
+      splits = d.pin_splits;
+      ka.kchunk = d.pin_kchunk;
+    }
     ka.nblk = ka.tiles * splits;
     p.splits = splits;
     if (splits > 1) {   // the deterministic slab reduction (+ epilogue) and the row-sum reduction follow
@@ -1857,7 +1896,7 @@ int gemm_plan(const GemmDesc& d, GemmPlan& p) {
     return SRK_OK;
   };
   // 256 x 256 tiles of one batch entry (the ping-pong kernels' grid)
-  const int64_t tiles256 = ((d.M + 255) / 256) * ((d.N + 255) / 256);
+  const int64_t tiles256 = ((PM + 255) / 256) * ((d.N + 255) / 256);
 
   if (ops16) {
     SRK_REQUIRE(d.A16 && d.B16 && d.C && prec != kPrecF32 && !d.rowsum && (d.batch == 1 || d.bias_mode == 0),
@@ -1871,7 +1910,7 @@ int gemm_plan(const GemmDesc& d, GemmPlan& p) {
                 SRK_ERR_INVALID, "gemm: 16-bit operands need 16-B aligned rows of 8-element multiples");
     SRK_REQUIRE(d.K > 0, SRK_ERR_INVALID, "gemm: 16-bit operands need K > 0");
     // the LDS-DMA ping-pong kernel wherever its 256 x 256 tile fills the chip (srk option overrides)
-    const int kern = g_opt_gemm16_kernel ? g_opt_gemm16_kernel : (d.M >= 1024 && d.N >= 256 ? 2 : 1);
+    const int kern = g_opt_gemm16_kernel ? g_opt_gemm16_kernel : (PM >= 1024 && d.N >= 256 ? 2 : 1);
     if (kern == 2 || env.h16_cfg == 5 || d.batch > 1) {   // only g16 is batched
       const TileFn k = with_trans(d.ta, d.tb, [&](auto ta, auto tb) -> TileFn {
         return p.f16 ? gemm_g16_kernel<decltype(ta)::value, decltype(tb)::value, true>
@@ -1885,7 +1924,7 @@ int gemm_plan(const GemmDesc& d, GemmPlan& p) {
       // measured (profiles/r01zk_gemm_h16_cfg*.txt): 256 x 256 on x W^T and on the weight gradients
       // (TA != TB: gi 143 vs 148 us, dW_ih 128 vs 137), 256 x 128 on dx (204 tiles of 256 x 256 leave
       // CUs idle: 255 vs 147 us), 128 x 128 below 1024 rows
-      const int cfg = env.h16_cfg ? env.h16_cfg : d.M < 1024 ? 1 : (d.ta != d.tb && d.N >= 256) ? 4 : 3;
+      const int cfg = env.h16_cfg ? env.h16_cfg : PM < 1024 ? 1 : (d.ta != d.tb && d.N >= 256) ? 4 : 3;
       const Variant v = with_trans(d.ta, d.tb, [&](auto ta, auto tb) {
         return h16_variant<decltype(ta)::value, decltype(tb)::value>(cfg, p.f16);
       });
@@ -1900,7 +1939,7 @@ int gemm_plan(const GemmDesc& d, GemmPlan& p) {
   SRK_REQUIRE(d.bias_mode == 0 || d.bias, SRK_ERR_INVALID, "gemm: bias_mode without bias");
   // One dimension <= 16: the VALU skinny kernels.  Sizes keep each kernel's per-thread loop short and its
   // streamed operand a few MB at most.
-  if (g_opt_gemm_skinny && d.batch == 1 && d.plan_batch <= 1 && d.K > 0) {
+  if (g_opt_gemm_skinny && d.batch == 1 && d.plan_batch <= 1 && d.plan_M == 0 && d.pin_splits == 0 && d.K > 0) {
     if (d.N <= 16 && !d.ta && d.M <= 65535 * 16 && d.M * d.K <= (int64_t)1 << 24) p.skinny = 0;
     else if (d.M <= 16 && !d.tb && d.K <= 1024 && d.N * d.K <= (int64_t)1 << 24) p.skinny = 1;
     else if (d.K <= 16 && !d.tb && d.M <= 65535 && d.M * d.N <= (int64_t)1 << 24) p.skinny = 2;
@@ -1931,7 +1970,7 @@ int gemm_plan(const GemmDesc& d, GemmPlan& p) {
     p.vec = vec && ext_a < kExtBuf && ext_b < kExtBuf && d.batch == 1;
     // measured (profiles/r01zf_gemm_bench_bf16_cfg*.txt): 256 x 128 tiles win whenever an operand is
     // row-contiguous (dx, dW: 12-25 %), the 128 x 128 tile on the x W^T projection (both k-contiguous)
-    const int cfg = env.lp_cfg ? env.lp_cfg : (d.M >= 1024 && !(!d.ta && d.tb)) ? 3 : 1;
+    const int cfg = env.lp_cfg ? env.lp_cfg : (PM >= 1024 && !(!d.ta && d.tb)) ? 3 : 1;
     const Variant v = with_trans(d.ta, d.tb, [&](auto ta, auto tb) {
       return lp_variant<decltype(ta)::value, decltype(tb)::value>(cfg, p.vec, p.f16);
     });
@@ -1948,7 +1987,7 @@ int gemm_plan(const GemmDesc& d, GemmPlan& p) {
   // 8 % slower on the x W^T projection (NT) and on the 12-tile dW_hh grid (split 16); batched
   // launches (the BiGRU's two dW_hh) and row sums over a batch only exist on the ping-pong kernel
   const int kern32 = g_opt_gemm32_kernel ? g_opt_gemm32_kernel
-                                         : (!d.tb && ((d.M >= 2048 && d.N >= 1024) || d.batch > 1 || d.plan_batch > 1) ? 2 : 1);
+                                         : (!d.tb && ((PM >= 2048 && d.N >= 1024) || d.batch > 1 || d.plan_batch > 1) ? 2 : 1);
   SRK_REQUIRE(!d.rowsum || d.batch == 1 || (p32_ok && kern32 == 2), SRK_ERR_INVALID,
               "gemm: batched row sums need the fp32 ping-pong kernel (16-B operand rows)");
   if (p32_ok && kern32 == 2) {
@@ -1956,7 +1995,10 @@ int gemm_plan(const GemmDesc& d, GemmPlan& p) {
     const int64_t ki = (d.K + kP32BK - 1) / kP32BK;
     // stream-K where one round of 256 x 256 tiles leaves CUs idle but covers at least half of them
     // (dx of the BiGRU layers: 204 tiles on 256 CUs), K long enough to split
-    p.streamk = g_opt_gemm_streamk && pb == 1 && !d.no_split && !d.rowsum && tiles < kCUs && tiles * 2 >= kCUs && ki >= 32;
+    p.streamk = g_opt_gemm_streamk && pb == 1 && !d.no_split && !d.rowsum && tiles < kCUs && tiles * 2 >= kCUs && ki >= 32 &&
+                d.pin_splits == 0;
+    // (a stream-K run's cuts depend on the tile index: no part of such a GEMM can repeat its bits)
+    SRK_REQUIRE(!(p.streamk && d.plan_M > d.M), SRK_ERR_INVALID, "gemm: plan_M names a stream-K GEMM");
     const TileFn k = with_trans(d.ta, d.tb, [](auto ta, auto tb) -> TileFn {
       return gemm_p32_kernel<decltype(ta)::value, decltype(tb)::value>;
     });
@@ -1975,10 +2017,10 @@ int gemm_plan(const GemmDesc& d, GemmPlan& p) {
 
   // 256 x 128 tiles (one 8-wave workgroup per CU, 110 KB of LDS) halve the L2 -> CU operand
   // traffic per flop of the 128 x 128 tile; used when the grid still fills the chip several times
-  const int64_t t256 = ((d.M + 255) / 256) * ((d.N + 127) / 128) * d.batch;
-  const bool big = env.tile ? env.tile == 256 : (d.M >= 2048 && d.N >= 128 && d.K >= 256 && (t256 >= 512 || d.K >= 4096));
-  const int64_t big_tiles = ((d.M + 127) / 128) * ((d.N + 127) / 128) * d.batch;
-  const int bm = big ? 256 : (d.M > 64 && d.N > 64 && (big_tiles >= 64 || d.K >= 2048)) ? 128 : 64;
+  const int64_t t256 = ((PM + 255) / 256) * ((d.N + 127) / 128) * d.batch;
+  const bool big = env.tile ? env.tile == 256 : (PM >= 2048 && d.N >= 128 && d.K >= 256 && (t256 >= 512 || d.K >= 4096));
+  const int64_t big_tiles = ((PM + 127) / 128) * ((d.N + 127) / 128) * d.batch;
+  const int bm = big ? 256 : (PM > 64 && d.N > 64 && (big_tiles >= 64 || d.K >= 2048)) ? 128 : 64;
   // 8 waves (4 per SIMD at 2 workgroups / CU) cover the k-tile staging + barrier phases better
   // (measured: weight-gradient GEMMs +4..17 %); the x W^T projection shape keeps 4.  The 64 x 64 tile
   // exists with 4 waves only, whatever its detail string states.
@@ -2024,17 +2066,39 @@ void gemm_plan_detail(const GemmPlan& p, const GemmDesc& d, char (&out)[96]) {
 
 // Run a plan: scratch (a growth step's device synchronization stays outside the timed scope), kernel arguments,
 // the profiler scope, the kernel, then the stream-K fixup and the split reductions it planned.
-int gemm_launch(const GemmPlan& p, const GemmDesc& d, hipStream_t s) {
-  if (p.family == kFamNone) return SRK_OK;
+// The plan's kernel arguments with its scratch placed at `scratch` (plan_scratch(p) floats).
+size_t plan_scratch(const GemmPlan& p) { return p.slab_floats + p.rs_floats + p.sk_floats; }
+KernelArgs plan_args(const GemmPlan& p, const GemmDesc& d, float* scratch) {
   KernelArgs ka = p.ka;
   ka.d = d;
-  if (const size_t need = p.slab_floats + p.rs_floats + p.sk_floats) {
-    float* scratch = nullptr;
+  if (p.slab_floats) ka.partial = scratch;
+  if (p.rs_floats) ka.rs_partial = scratch + p.slab_floats;
+  if (p.sk_floats) ka.sk_slab = scratch + p.slab_floats + p.rs_floats;
+  return ka;
+}
+// The reductions a split launch planned: the slabs in split order with the epilogue, then the row sums.
+int plan_reduce(const GemmPlan& p, const GemmDesc& d, const KernelArgs& ka, hipStream_t s) {
+  if (!p.reduce) return SRK_OK;
+  const int64_t n = d.M * d.N;
+  if (p.reduce == 4)
+    hipLaunchKernelGGL(splitk_reduce4_kernel, dim3((unsigned)((n / 4 + 255) / 256), (unsigned)d.batch), dim3(256), 0,
+                       s, d, ka.partial, p.splits);
+  else
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)d.batch), dim3(256), 0, s, d,
+                       ka.partial, p.splits);
+  if (p.rowsum_reduce)
+    hipLaunchKernelGGL(rowsum_reduce_kernel, dim3((unsigned)((d.M + 255) / 256), (unsigned)d.batch), dim3(256), 0, s,
+                       d.rowsum, d.rowsum_beta, ka.rs_partial, d.M, p.splits, d.sRS);
+  SRK_CHECK_HIP(hipGetLastError());
+  return SRK_OK;
+}
+
+int gemm_launch(const GemmPlan& p, const GemmDesc& d, hipStream_t s) {
+  if (p.family == kFamNone) return SRK_OK;
+  float* scratch = nullptr;
+  if (const size_t need = plan_scratch(p))
     if (int rc = g_scratch.get(need, &scratch)) return rc;
-    if (p.slab_floats) ka.partial = scratch;
-    if (p.rs_floats) ka.rs_partial = scratch + p.slab_floats;
-    if (p.sk_floats) ka.sk_slab = scratch + p.slab_floats + p.rs_floats;
-  }
+  const KernelArgs ka = plan_args(p, d, scratch);
   ProfScope prof(p.name, s, p.flops);
   prof.bytes(p.bytes);
   if (prof.on()) {
@@ -2046,23 +2110,147 @@ int gemm_launch(const GemmPlan& p, const GemmDesc& d, hipStream_t s) {
   else hipLaunchKernelGGL(p.kernel, p.grid, p.block, 0, s, ka);
   if (p.streamk) hipLaunchKernelGGL(sk_fixup_kernel, dim3((unsigned)ka.tiles * kSkFixupSlices), dim3(256), 0, s, ka);
   SRK_CHECK_HIP(hipGetLastError());
-  if (p.reduce) {
-    const int64_t n = d.M * d.N;
-    if (p.reduce == 4)
-      hipLaunchKernelGGL(splitk_reduce4_kernel, dim3((unsigned)((n / 4 + 255) / 256), (unsigned)d.batch), dim3(256), 0,
-                         s, d, ka.partial, p.splits);
-    else
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)d.batch), dim3(256), 0, s, d,
-                         ka.partial, p.splits);
-    if (p.rowsum_reduce)
-      hipLaunchKernelGGL(rowsum_reduce_kernel, dim3((unsigned)((d.M + 255) / 256), (unsigned)d.batch), dim3(256), 0, s,
-                         d.rowsum, d.rowsum_beta, ka.rs_partial, d.M, p.splits, d.sRS);
-    SRK_CHECK_HIP(hipGetLastError());
+  return plan_reduce(p, d, ka, s);
+}
+
+// dst rows of a packed operand (PackPlan): grid.y = 0 the A rows (live rows copied, every other row zero),
+// grid.y = 1 the B rows (the kept blocks' rows below K, zeros elsewhere).  One 16-B vector per thread.
+__global__ __launch_bounds__(256) void pack_rows_kernel(PackPlan pp, const float* __restrict__ A, int64_t lda, int64_t wa,
+                                                        const float* __restrict__ B, int64_t ldb, int64_t wb,
+                                                        float* __restrict__ Ap, float* __restrict__ Bp) {
+  const bool isb = blockIdx.y != 0;
+  const int64_t w4 = (isb ? wb : wa) / 4, i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= pp.nslabs * pp.pslab * w4) return;
+  const int64_t kp = i / w4, c = (i - kp * w4) * 4;
+  bool live;
+  const int64_t row = pp.src(kp, &live);
+  v4f v = v4f{0.f, 0.f, 0.f, 0.f};
+  if (isb) {
+    if (row >= 0 && row < pp.K) v = ld4(B + row * ldb + c);
+    st4(Bp + kp * wb + c, v);
+  } else {
+    if (live) v = ld4(A + row * lda + c);
+    st4(Ap + kp * wa + c, v);
   }
-  return SRK_OK;
 }
 
 }  // namespace
+
+int pack_plan(int64_t K, int64_t slab, int64_t first, int64_t stride, int64_t count, PackPlan& p) {
+  SRK_REQUIRE(K >= 1 && count >= 1 && slab >= 16 && slab % 16 == 0 && first >= 0 && stride >= 8 &&
+                  K < ((int64_t)1 << 40) && count <= K && first + (count - 1) * stride < K,
+              SRK_ERR_INVALID, "pack_plan: need K, count >= 1, slab a positive multiple of 16, first >= 0, stride >= 8 "
+              "and every live row below K");
+  p = PackPlan{};
+  p.K = K; p.slab = slab; p.first = first; p.stride = stride; p.count = count;
+  p.nslabs = (K + slab - 1) / slab;
+  int64_t most = 0;
+  for (int64_t s = 0; s < p.nslabs; ++s) most = std::max(most, p.lo(s + 1) - p.lo(s));
+  p.pslab = (most * 8 + 15) / 16 * 16;
+  return SRK_OK;
+}
+
+int gemm_pack_rows(const PackPlan& p, const float* A, int64_t lda, int64_t wa, const float* B, int64_t ldb, int64_t wb,
+                   float* Ap, float* Bp, hipStream_t s) {
+  SRK_REQUIRE(A && B && Ap && Bp && wa > 0 && wb > 0 && wa % 4 == 0 && wb % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 &&
+                  ((uintptr_t)A | (uintptr_t)B | (uintptr_t)Ap | (uintptr_t)Bp) % 16 == 0 && p.pslab > 0,
+              SRK_ERR_INVALID, "gemm_pack_rows: operands must be 16-B aligned rows of 4-float multiples");
+  const int64_t rows = p.nslabs * p.pslab, n = rows * std::max(wa, wb) / 4;
+  SRK_REQUIRE((n + 255) / 256 <= INT32_MAX, SRK_ERR_INVALID, "gemm_pack_rows: too large");
+  ProfScope prof("gemm_pack_rows", s, 4.0 * (double)rows * (wa + wb));
+  hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)((n + 255) / 256), 2), dim3(256), 0, s, p, A, lda, wa, B, ldb, wb,
+                     Ap, Bp);
+  SRK_CHECK_HIP(hipGetLastError());
+  return SRK_OK;
+}
+
+bool gemm_group_enabled() {
+  static const bool on = [] {
+    const char* v = getenv("SRK_GEMM_GROUP");
+    return !(v && *v) || atoi(v) != 0;
+  }();
+  return on;
+}
+
+bool gemm_f32_pin_as(const GemmDesc& full, GemmDesc& part) {
+  GemmPlan pf, pp;
+  part.pin_splits = 0;
+  part.pin_kchunk = 0;
+  if (full.K != part.K || gemm_plan(full, pf) != SRK_OK || pf.family == kFamNone || pf.family == kFamSkinny || pf.streamk)
+    return false;
+  part.pin_splits = pf.splits;
+  part.pin_kchunk = pf.ka.kchunk;
+  if (gemm_plan(part, pp) == SRK_OK && pp.family == pf.family && pp.bk == pf.bk && pp.prec == pf.prec) return true;
+  part.pin_splits = 0;
+  part.pin_kchunk = 0;
+  return false;
+}
+
+bool gemm_f32_p32_split(const GemmDesc& d, int* splits, int64_t* kchunk) {
+  GemmPlan p;
+  if (gemm_plan(d, p) != SRK_OK || p.family != kFamP32 || p.streamk) return false;
+  *splits = p.splits;
+  *kchunk = p.ka.kchunk;
+  return true;
+}
+
+int gemm_f32_group(const GemmDesc* ds, int n, hipStream_t s) {
+  SRK_REQUIRE(ds && n >= 1 && n <= kGemmGroupMax, SRK_ERR_INVALID, "gemm_group: 1 .. %d members", kGemmGroupMax);
+  GemmPlan plans[kGemmGroupMax];
+  int order[kGemmGroupMax];
+  for (int i = 0; i < n; ++i) {
+    if (int rc = gemm_plan(ds[i], plans[i])) return rc;
+    SRK_REQUIRE(plans[i].family == kFamP32 && !plans[i].streamk && ds[i].batch == 1 && ds[i].ta == ds[0].ta &&
+                    ds[i].tb == ds[0].tb,
+                SRK_ERR_INVALID, "gemm_group: member %d is not a batch-1, non-stream-K gemm_p32_kernel launch of the "
+                "group's (ta, tb)", i);
+    order[i] = i;
+  }
+  // longest per-workgroup K first: the launch ends when its heaviest member does
+  const auto klen = [&](int i) { return std::min(plans[i].ka.kchunk, std::max<int64_t>(ds[i].K, 1)); };
+  std::stable_sort(order, order + n, [&](int a, int b) { return klen(a) > klen(b); });
+  size_t off[kGemmGroupMax], need = 0;
+  GroupArgs ga{};
+  int64_t nblk = 0;
+  for (int j = 0; j < n; ++j) {
+    const GemmPlan& p = plans[order[j]];
+    off[j] = need;
+    need += (plan_scratch(p) + 63) / 64 * 64;   // every member's pieces stay 16-B aligned
+    ga.first[j] = (int)nblk;
+    nblk = (nblk + p.ka.nblk + 7) / 8 * 8;      // the next member starts on XCD 0
+    SRK_REQUIRE(nblk <= (INT32_MAX >> 5), SRK_ERR_INVALID, "gemm_group: grid too large");
+  }
+  ga.n = n;
+  float* scratch = nullptr;
+  if (need)
+    if (int rc = g_scratch.get(need, &scratch)) return rc;   // ONE request: the pool hands out one buffer
+  double flops = 0.0, bytes = 0.0;
+  for (int j = 0; j < n; ++j) {
+    ga.m[j] = plan_args(plans[order[j]], ds[order[j]], scratch + off[j]);
+    flops += plans[order[j]].flops;
+    bytes += plans[order[j]].bytes;
+  }
+  ProfScope prof(plans[0].name, s, flops);
+  prof.bytes(bytes);
+  if (prof.on()) {
+    char detail[96];
+    int at = snprintf(detail, sizeof(detail), "gemm_p32_group<%c%c>", ds[0].ta ? 'T' : 'N', ds[0].tb ? 'T' : 'N');
+    for (int j = 0; j < n && at < (int)sizeof(detail); ++j) {
+      const GemmDesc& d = ds[order[j]];
+      at += snprintf(detail + at, sizeof(detail) - at, " %lldx%lldx%llds%d", (long long)d.M, (long long)d.N,
+                     (long long)d.K, plans[order[j]].splits);
+    }
+    prof.detail("%s", detail);
+  }
+  const auto kernel = with_trans(ds[0].ta, ds[0].tb, [](auto ta, auto tb) -> void (*)(GroupArgs) {
+    return gemm_p32_group_kernel<decltype(ta)::value, decltype(tb)::value>;
+  });
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(512), 0, s, ga);
+  SRK_CHECK_HIP(hipGetLastError());
+  for (int j = 0; j < n; ++j)
+    if (int rc = plan_reduce(plans[order[j]], ds[order[j]], ga.m[j], s)) return rc;
+  return SRK_OK;
+}
 
 bool gemm_f32_batched_rowsum_ok(const GemmDesc& d) {
   // batched row sums exist only on the fp32-operand ping-pong kernel; a batched launch spans batch - 1
@@ -2171,6 +2359,37 @@ extern "C" int srk_gemm_16_batched(int trans_a, int trans_b, int64_t M, int64_t 
   SRK_REQUIRE(srk::matmul_prec() != srk::kPrecF32, SRK_ERR_INVALID,
               "gemm_16_batched: set matmul_precision to bf16 / fp16");
   return srk::gemm_f32(d, srk::as_stream(stream));
+  SRK_API_END
+}
+
+// The zero-block packing plan (srk::pack_plan), host only: the kept 8-deep k blocks slab by slab.
+extern "C" int srk_gemm_pack_plan(int64_t K, int64_t slab, int64_t first, int64_t stride, int64_t count,
+                                  int64_t* blocks, int64_t blocks_cap, int64_t* slab_counts, int64_t slabs_cap,
+                                  int64_t* n_slabs, int64_t* packed_slab) {
+  SRK_API_BEGIN
+  SRK_REQUIRE(blocks && slab_counts && n_slabs && packed_slab && blocks_cap >= 0 && slabs_cap >= 0, SRK_ERR_INVALID,
+              "gemm_pack_plan: null pointer");
+  srk::PackPlan p;
+  if (int rc = srk::pack_plan(K, slab, first, stride, count, p)) return rc;
+  SRK_REQUIRE(blocks_cap >= count && slabs_cap >= p.nslabs, SRK_ERR_INVALID,
+              "gemm_pack_plan: need room for %lld blocks and %lld slabs", (long long)count, (long long)p.nslabs);
+  // read back through PackPlan::src, the function the gather kernel runs: block j of slab s is kept when its rows
+  // have a source
+  int64_t nb = 0;
+  for (int64_t s = 0; s < p.nslabs; ++s) {
+    slab_counts[s] = 0;
+    for (int64_t r = 0; r < p.pslab; r += 8) {
+      bool live;
+      const int64_t row = p.src(s * p.pslab + r, &live);
+      if (row < 0) continue;
+      SRK_REQUIRE(nb < blocks_cap, SRK_ERR_INTERNAL, "gemm_pack_plan: more kept blocks than live rows");
+      blocks[nb++] = row / 8;
+      ++slab_counts[s];
+    }
+  }
+  *n_slabs = p.nslabs;
+  *packed_slab = p.pslab;
+  return SRK_OK;
   SRK_API_END
 }
 

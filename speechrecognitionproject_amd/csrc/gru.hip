@@ -711,6 +711,11 @@ static int layer_fwd(const float* x, const void* x16_in, int64_t B, int64_t T, i
       g.B = wa; g.ldb = ink; g.tb = true;
       g.C = gi; g.ldc = 6 * H;
       g.bias = b_ih; g.bias_mode = 1;
+      if (top_last == 3) {   // the K split of the full projection: its bits at every shape
+        GemmDesc full = g;
+        full.N = 6 * H;
+        srk::gemm_f32_pin_as(full, g);
+      }
       if (int rc = srk::gemm_f32(g, s)) return rc;
     }
     if (rev_cell) {
@@ -721,7 +726,15 @@ static int layer_fwd(const float* x, const void* x16_in, int64_t B, int64_t T, i
       g.B = wa + 3 * H * ink; g.ldb = ink; g.tb = true;
       g.C = gi + (T - 1) * 6 * H + 3 * H; g.ldc = T * 6 * H;
       g.bias = b_ih + 3 * H; g.bias_mode = 1;
-      g.no_split = top_last == 3;   // mode 3: the full projection's sum order (wherever that GEMM runs unsplit)
+      if (top_last == 3) {   // mode 3: the full projection's sum order, its K split included; unsplit failing that
+        GemmDesc full;
+        full.M = BT; full.N = 6 * H; full.K = ink;
+        full.A = xa; full.lda = ink;
+        full.B = wa; full.ldb = ink; full.tb = true;
+        full.C = gi; full.ldc = 6 * H;
+        full.bias = b_ih; full.bias_mode = 1;
+        if (!srk::gemm_f32_pin_as(full, g)) g.no_split = true;
+      }
       if (int rc = srk::gemm_f32(g, s)) return rc;
     }
   }
@@ -892,7 +905,59 @@ static int layer_bwd(const float* x, const void* x16_in, int64_t B, int64_t T, i
   // dW_ih / dx GEMMs (their sums' order, so their bits) and drops only the reverse dW_hh
   const bool rev_last = top_last == 1 || top_last == 2;
   const Mat m_dgi_rev = m_dgi.at((T - 1) * 6 * H + 3 * H);
-  {  // dW_ih_cat[6H, in] = dgi^T [6H, BT] * x [BT, in] (the forward's padded x); fp32: db_ih = the row sums of dgi^T
+  // Mode 3, grouped (last-step top layer): the full dW_ih GEMM multiplies the reverse half's
+  // BT - B zero rows, and the forward dW_hh planned as the two-direction launch fills half of the CUs.  Both keep
+  // their bits as parts: the dW_ih forward half on the full GEMM's kernel and K split, the reverse half with its
+  // all-zero 8-deep k blocks deleted slab by slab (PackPlan), the dW_hh as before; the three share one launch.
+  bool grouped = false;
+  if (top_last == 3 && !h16 && T >= 16 && srk::gemm_group_enabled()) {
+    GemmDesc full;   // the one dW_ih GEMM of the ungrouped path
+    full.M = 6 * H; full.N = ld; full.K = BT;
+    full.A = dgi; full.lda = 6 * H; full.ta = true;
+    full.B = m_x.f; full.ldb = ld;
+    full.C = pad ? dwpad : dw_ih; full.ldc = ld; full.beta = pad ? 0.f : beta;
+    full.rowsum = db_ih; full.rowsum_beta = beta;
+    GemmDesc hh;     // the two-direction dW_hh launch the forward-only one is planned as
+    hh.M = 3 * H; hh.N = H; hh.K = BT - 1;
+    hh.ta = true; hh.lda = 3 * H; hh.ldb = 2 * H;
+    hh.A = dgh + 3 * H; hh.B = y;
+    hh.C = dw_hh; hh.ldc = H; hh.beta = beta;
+    hh.batch = 2; hh.sA = BT * 3 * H - 3 * H; hh.sB = 3 * H; hh.sC = 3 * H * H;
+    hh.rowsum = db_hh; hh.rowsum_beta = beta; hh.sRS = 3 * H;
+    int splits = 0;
+    int64_t kchunk = 0;
+    srk::PackPlan pp;
+    if (srk::gemm_f32_p32_split(full, &splits, &kchunk) && splits > 1 && srk::g_opt_gru_dwhh_batched &&
+        srk::gemm_f32_batched_rowsum_ok(hh) && srk::pack_plan(BT, kchunk, T - 1, T, B, pp) == SRK_OK &&
+        pp.nslabs == splits) {
+      grouped = true;
+      const int64_t rows = pp.nslabs * pp.pslab;
+      float* packed = nullptr;   // A' [rows][3H] | B' [rows][ld]
+      if ((rc = srk::g_gs.get((size_t)rows * (3 * H + ld), &packed))) return rc;
+      if ((rc = srk::gemm_pack_rows(pp, dgi + 3 * H, 6 * H, 3 * H, m_x.f, ld, ld, packed, packed + rows * 3 * H, s)))
+        return rc;
+      GemmDesc m[3];
+      m[0] = full;   // the forward half: rows 0 .. 3H of the full GEMM
+      m[0].M = 3 * H; m[0].plan_M = 6 * H;
+      m[1] = hh;     // the forward direction of the two-direction launch
+      m[1].batch = 1; m[1].plan_batch = 2;
+      m[2] = m[0];   // the reverse half over the packed K
+      m[2].K = rows; m[2].pin_splits = (int)pp.nslabs; m[2].pin_kchunk = pp.pslab;
+      m[2].A = packed; m[2].lda = 3 * H;
+      m[2].B = packed + rows * 3 * H;
+      m[2].C = full.C + 3 * H * ld;
+      m[2].rowsum = db_ih + 3 * H;
+      if ((rc = srk::gemm_f32_group(m, 3, s))) return rc;
+      if (pad && (rc = srk::launch256(srk::unpad_cols_kernel, 6 * H * in, s, dwpad, 6 * H, ld, dw_ih, in, accumulate)))
+        return rc;
+      if (!accumulate) {   // dW_hh[1] = 0; db_hh[1] = the column sums of dgh_edge[1] below
+        SRK_CHECK_HIP(hipMemsetAsync(dw_hh + 3 * H * H, 0, sizeof(float) * 3 * H * H, s));
+        SRK_CHECK_HIP(hipMemsetAsync(db_hh + 3 * H, 0, sizeof(float) * 3 * H, s));
+      }
+    }
+  }
+  if (!grouped) {
+    // dW_ih_cat[6H, in] = dgi^T [6H, BT] * x [BT, in] (the forward's padded x); fp32: db_ih = the row sums of dgi^T
     GemmDesc g;
     g.M = rev_last ? 3 * H : 6 * H; g.N = ld; g.K = BT;
     set_a(g, m_dgi); g.lda = 6 * H; g.ta = true;
@@ -911,7 +976,7 @@ static int layer_bwd(const float* x, const void* x16_in, int64_t B, int64_t T, i
     if (pad && (rc = srk::launch256(srk::unpad_cols_kernel, 6 * H * in, s, dwpad, 6 * H, ld, dw_ih, in, accumulate)))
       return rc;
   }
-  if (!dw_parts) {   // (else the recurrence kernel accumulated it: dwhh_dbias_reduce_kernel above)
+  if (!dw_parts && !grouped) {   // (else the recurrence kernel accumulated it: dwhh_dbias_reduce_kernel above)
     // dW_hh[dir][3H, H] = sum_(b,t) dgh[b][t]^T h_prev[b][t]; h_prev of row (b,t) is y row (b,t-1)
     // (dir 0) or (b,t+1) (dir 1); the edge rows of dgh are zero so the batch seams contribute 0.
     // fp32: db_hh = row sums of dgh^T (fused) + the edge rows kept aside in dgh_edge.  Both directions run
