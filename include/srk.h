@@ -264,6 +264,22 @@ int srk_gemm_plan_describe(int trans_a, int trans_b, int64_t M, int64_t N, int64
 int srk_gemm_pack_plan(int64_t K, int64_t slab, int64_t first, int64_t stride, int64_t count, int64_t* blocks,
                        int64_t blocks_cap, int64_t* slab_counts, int64_t slabs_cap, int64_t* n_slabs,
                        int64_t* packed_slab);
+/* C [M,N] (ldc) = A [M,K] (lda) * B [K,N] (ldb) where columns k >= k_live of A are zero in every row but the `count`
+ * live rows first, first + stride, ... (stride >= 8, all below M): the stream-K launch of srk_gemm_f32 for these
+ * arguments without the K-tiles known to be zero, its cuts unmoved, then the live rows over the full K.  Bit for
+ * bit what srk_gemm_f32 (alpha 1, beta 0, no bias) gives on the zero-filled A, up to the sign of a zero and for
+ * finite B; columns k >= k_live of the other rows are never read.  SRK_ERR_INVALID unless the product plans as the
+ * fp32 stream-K ping-pong kernel and k_live is a multiple of 16 in (0, K).                              */
+int srk_gemm_f32_klive(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb,
+                       float* C, int64_t ldc, int64_t k_live, int64_t first, int64_t stride, int64_t count,
+                       void* stream);
+/* Host only, no GPU needed: what srk_gemm_f32_klive keeps of the stream-K plan of a packed (M, N, K) product:
+ * *tiles output tiles of *ktiles 16-deep K-tiles each, cut into *wgs equal runs; kept[w] = the K-tiles workgroup w
+ * still executes (kept_cap >= *wgs), live_runs[t] = the runs that execute K-tiles of tile t (runs_cap >= *tiles).
+ * beta and bias_mode are those of the GEMM asked for; SRK_ERR_INVALID where srk_gemm_f32_klive would refuse.  */
+int srk_gemm_klive_plan(int64_t M, int64_t N, int64_t K, int64_t k_live, int64_t first, int64_t stride, int64_t count,
+                        float beta, int bias_mode, int64_t* kept, int64_t kept_cap, int64_t* live_runs,
+                        int64_t runs_cap, int64_t* tiles, int64_t* ktiles, int64_t* wgs);
 
 /* ---------------------------------------------------------------- K5: bidirectional GRU layer
  * nn.GRU(in, H, bidirectional=True, batch_first=True), one layer, PyTorch gate order [r; z; n],

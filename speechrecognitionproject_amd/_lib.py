@@ -70,6 +70,10 @@ _SIGS = {
                                _I64],
     "srk_gemm_pack_plan": [_I64, _I64, _I64, _I64, _I64, ctypes.POINTER(_I64), _I64, ctypes.POINTER(_I64), _I64,
                            ctypes.POINTER(_I64), ctypes.POINTER(_I64)],
+    "srk_gemm_f32_klive": [_I64, _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P],
+    "srk_gemm_klive_plan": [_I64, _I64, _I64, _I64, _I64, _I64, _I64, _F, _I, ctypes.POINTER(_I64), _I64,
+                            ctypes.POINTER(_I64), _I64, ctypes.POINTER(_I64), ctypes.POINTER(_I64),
+                            ctypes.POINTER(_I64)],
     "srk_gru_workspace_floats": [_I64, _I64, _I64, _I64, _I],
     "srk_gru_layer_fwd": [_P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P],
     "srk_gru_layer_bwd": [_P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
@@ -236,6 +240,16 @@ def gemm_pack_plan(K, slab, first, stride, count):
         out.append([int(b) for b in blocks[at:at + counts[s]]])
         at += counts[s]
     return out, int(pslab.value)
+
+
+def gemm_klive_plan(M, N, K, k_live, first, stride, count, beta=0.0, bias_mode=0):
+    """srk_gemm_klive_plan: (tiles, K-tiles per tile, [K-tiles workgroup w keeps], [live runs of tile t])."""
+    nt = max(-(-int(M) // 256) * -(-int(N) // 256), 1)
+    kept, runs = (_I64 * 1024)(), (_I64 * nt)()
+    tiles, ktiles, wgs = _I64(0), _I64(0), _I64(0)
+    call("srk_gemm_klive_plan", M, N, K, k_live, first, stride, count, beta, bias_mode, kept, 1024, runs, nt,
+         ctypes.byref(tiles), ctypes.byref(ktiles), ctypes.byref(wgs))
+    return tiles.value, ktiles.value, [int(k) for k in kept[:wgs.value]], [int(r) for r in runs[:tiles.value]]
 
 
 def scratch_generation():

@@ -40,6 +40,9 @@ struct GemmDesc {
   int64_t plan_M = 0;
   int pin_splits = 0;
   int64_t pin_kchunk = 0;
+  // k_live > 0 (gemm_f32_klive only; gemm_plan ignores these four): columns k >= k_live of op(A) are zero in every
+  // row but the live rows live_first, live_first + live_stride, ... (live_count of them; stride >= 8 as in PackPlan).
+  int64_t k_live = 0, live_first = 0, live_stride = 0, live_count = 0;
 };
 
 // Enqueue on `stream`; returns SRK_OK or an srk_status.
@@ -63,6 +66,21 @@ constexpr int kGemmGroupMax = 4;
 int gemm_f32_group(const GemmDesc* ds, int n, hipStream_t stream);
 // Process-start switch SRK_GEMM_GROUP (default 1): 0 = callers issue their part-GEMMs as before (A/B measurements).
 bool gemm_group_enabled();
+
+// A stream-K gemm_p32_kernel GEMM whose op(A) is zero at k >= d.k_live in all rows but d's live rows, without the
+// K-tiles known to be zero: the launch of gemm_f32(d) with the same cuts, every segment clipped to k_live (a
+// segment past it does nothing), the fixup over the live runs, then one kernel that recomputes the live rows over
+// the full K with the full plan's cuts and run order.  An element's bits depend on its accumulator chain and on
+// where K is cut, and a K-tile whose A rows are zero leaves every chain as it was, so the result equals
+// gemm_f32(d) on the zero-filled operand bit for bit -- up to the sign of a zero (x + (+0) against no add), and for
+// finite B only (the full GEMM turns 0 * inf into NaN, this one never multiplies it).  Columns k >= k_live of the
+// dead rows are never read.  gemm_f32_klive_ok: the plan of d is the fp32 stream-K gemm_p32_kernel, non-transposed
+// A, batch 1, alpha 1, beta 0, no bias, no row sums, k_live a positive multiple of the K-tile below K, stride >= 8,
+// every live row below M; gemm_f32_klive refuses anything else with SRK_ERR_INVALID.
+bool gemm_f32_klive_ok(const GemmDesc& d);
+int gemm_f32_klive(const GemmDesc& d, hipStream_t stream);
+// Process-start switch SRK_GEMM_KLIVE (default 1): 0 = callers keep the full GEMM (A/B measurements).
+bool gemm_klive_enabled();
 
 // Zero-block packing of a K dimension whose only nonzero A rows are `count` live rows first, first + stride, ...
 // (stride >= 8, so each sits in an 8-aligned k block of its own).  Every 8-block holding a live row is kept, in

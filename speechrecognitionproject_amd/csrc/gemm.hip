@@ -40,7 +40,12 @@ struct KernelArgs {
   int sk_wgs;
   int sk_ki;
   float* sk_slab;
+  // gemm_f32_klive: the K-tiles of a tile that are executed, d.k_live / BK (0 = all sk_ki): a segment ends there,
+  // one that begins at or past it is skipped, and a tile is partial when its first live_ki K-tiles span runs
+  int live_ki;
 };
+// the K-tiles of a stream-K tile that the launch executes
+__host__ __device__ __forceinline__ int sk_live(const KernelArgs& ka) { return ka.live_ki > 0 ? ka.live_ki : ka.sk_ki; }
 
 // tile index t (one split's grid, grouped order) -> (tile row, tile column); see map_tile
 __device__ __forceinline__ void tile_of(int t, int tiles_m, int tiles_n, int group_m, int& tm, int& tn) {
@@ -52,8 +57,8 @@ __device__ __forceinline__ void tile_of(int t, int tiles_m, int tiles_n, int gro
   tn = tin / gm;
 }
 // stream-K: run w covers K-tile iterations [w total / W, (w + 1) total / W); the run holding iteration it
-__device__ __forceinline__ int64_t sk_begin(int64_t w, int64_t total, int64_t W) { return w * total / W; }
-__device__ __forceinline__ int sk_owner(int64_t it, int64_t total, int64_t W) { return (int)(((it + 1) * W - 1) / total); }
+__host__ __device__ __forceinline__ int64_t sk_begin(int64_t w, int64_t total, int64_t W) { return w * total / W; }
+__host__ __device__ __forceinline__ int sk_owner(int64_t it, int64_t total, int64_t W) { return (int)(((it + 1) * W - 1) / total); }
 
 // Epilogue shared by the tile kernels.  32x32 accumulator: col = lane & 31,
 // row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).  Split-K launches write the raw fp32 slab.
@@ -1331,21 +1336,35 @@ struct P32Half {
   // k offset within the K-tile, rows in range
   __device__ static __forceinline__ void src(int piece, int lane, int64_t r0, int64_t rows, int64_t ld, unsigned& voff,
                                              int& kk, bool& row_ok) {
-    const int p = piece * 64 + lane;
+    int row;
+    unit(piece * 64 + lane, row, kk);
+    voff = (unsigned)((KC ? (r0 + row) * ld + kk : kk * ld + r0 + row) * 4);
+    row_ok = r0 + row < rows;
+  }
+  // 16-B unit p of the image (at float 4 p): its row (KC) or the first of its 4 rows (TR), its k offset in the K-tile
+  __device__ static __forceinline__ void unit(int p, int& row, int& kk) {
     if (KC) {   // p = row * 4 + slot
-      const int row = p >> 2, kc = (p & 3) ^ ((row >> 2) & 3);
-      voff = (unsigned)(((r0 + row) * ld + kc * 4) * 4);
-      kk = kc * 4;
-      row_ok = r0 + row < rows;
+      row = p >> 2;
+      kk = ((p & 3) ^ ((row >> 2) & 3)) * 4;
     } else {    // p = k * 32 + unit (4 rows)
-      const int k = p >> 5, u = p & 31;
-      voff = (unsigned)((k * ld + r0 + u * 4) * 4);
-      kk = k;
-      row_ok = r0 + u * 4 < rows;
+      kk = p >> 5;
+      row = (p & 31) * 4;
     }
   }
   __device__ static __forceinline__ int64_t kstep_bytes(int64_t ld) { return KC ? 4 : 4 * ld; }
 };
+
+// One 8-deep k block of the chain: sub-step ss multiplies element ss of every fragment (k = 8 kb + 4 h + ss in
+// half-wave h, P32Half::frag).  The one place that fixes the k order of gemm_p32_kernel's sums.
+template <int TM, int TN>
+__device__ __forceinline__ void p32_mma_block(const v4f (&fa)[TM], const v4f (&fb)[TN], f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+  for (int ss = 0; ss < 4; ++ss)
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][ss], fb[j][ss], acc[i][j], 0, 0, 0);
+}
 
 // The kernel's body for block `blk` of ka's grid and batch entry z: gemm_p32_kernel runs it with its own block
 // index, gemm_p32_group_kernel with the index inside the member it picked.
@@ -1386,14 +1405,18 @@ __device__ __forceinline__ void gemm_p32_body(const KernelArgs& ka, const int bl
   if (sk) {
     if (sk_it >= sk_end) break;
     const int t = (int)(sk_it / ka.sk_ki);
-    const int64_t t0 = (int64_t)t * ka.sk_ki, kt_end = min((int64_t)ka.sk_ki, sk_end - t0);
-    kb0 = (sk_it - t0) * BK;
+    // live: the K-tiles of the tile that are executed (all of them but under gemm_f32_klive); the cuts stay where
+    // they are, a segment is clipped to them or, beginning past them, skipped by the whole workgroup
+    const int64_t t0 = (int64_t)t * ka.sk_ki, live = sk_live(ka), kt_end = min(live, sk_end - t0);
+    const int64_t it0 = sk_it;
+    sk_it = t0 + ka.sk_ki;
+    if (it0 - t0 >= live) continue;
+    kb0 = (it0 - t0) * BK;
     ke = min(d.K, kt_end * BK);
     tile_of(t, ka.tiles_m, ka.tiles_n, ka.group_m, tm, tn);
-    const int w0 = sk_owner(t0, sk_total, ka.sk_wgs), w1 = sk_owner(t0 + ka.sk_ki - 1, sk_total, ka.sk_wgs);
-    const int wme = sk_owner(sk_it, sk_total, ka.sk_wgs);
+    const int w0 = sk_owner(t0, sk_total, ka.sk_wgs), w1 = sk_owner(t0 + live - 1, sk_total, ka.sk_wgs);
+    const int wme = sk_owner(it0, sk_total, ka.sk_wgs);
     if (w1 > w0) seg_slab = ka.sk_slab + (int64_t)(wme - w0) * d.M * d.N;   // a partial tile
-    sk_it = t0 + ka.sk_ki;
     if (!first_seg) __syncthreads();   // the previous segment's epilogue is done with the LDS ring
   } else {
     if (!first_seg) break;
@@ -1488,12 +1511,7 @@ __device__ __forceinline__ void gemm_p32_body(const KernelArgs& ka, const int bl
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       bar();
       __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int ss = 0; ss < 4; ++ss)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][ss], fb[j][ss], acc[i][j], 0, 0, 0);
+      p32_mma_block(fa, fb, acc);
       __builtin_amdgcn_s_setprio(0);
       if (do_rs) {
 #pragma unroll
@@ -1555,7 +1573,8 @@ __global__ __launch_bounds__(256) void sk_fixup_kernel(KernelArgs ka) {
   const GemmDesc& d = ka.d;
   const int t = blockIdx.x / kSkFixupSlices, slice = blockIdx.x - t * kSkFixupSlices;
   const int64_t total = (int64_t)ka.tiles * ka.sk_ki, t0 = (int64_t)t * ka.sk_ki;
-  const int w0 = sk_owner(t0, total, ka.sk_wgs), w1 = sk_owner(t0 + ka.sk_ki - 1, total, ka.sk_wgs);
+  // the runs that executed K-tiles of the tile (gemm_f32_klive: of its first live_ki), as the body decides
+  const int w0 = sk_owner(t0, total, ka.sk_wgs), w1 = sk_owner(t0 + sk_live(ka) - 1, total, ka.sk_wgs);
   if (w1 == w0) return;
   int tm, tn;
   tile_of(t, ka.tiles_m, ka.tiles_n, ka.group_m, tm, tn);
@@ -1616,6 +1635,113 @@ __global__ __launch_bounds__(256) void sk_fixup_kernel(KernelArgs ka) {
       if (d.beta != 0.f) v += d.beta * *c;
       *c = v;
     }
+  }
+}
+
+// gemm_f32_klive's completion: the live rows of C over the FULL K, with the full plan's bits.  One workgroup per
+// tile of the plan gathers the tile's live rows (stride >= 8: at most 32) into one 32-row A block and gives each of
+// its 8 waves 32 of the tile's 256 columns.  K is walked as the body walks it (P32Half::frag fragments of the same
+// images, p32_mma_block), every run of the tile from zero accumulators, the runs' partial sums added in run order
+// (sk_fixup_kernel's (p0 + p1) + p2): the accumulator chain and the cuts of gemm_p32_kernel, so its bits.  Images
+// are staged through registers, kLiveKT K-tiles per stage, two stages in LDS; units past K, N or the live rows
+// are zeros.  alpha 1, beta 0, no bias (gemm_f32_klive_ok).
+constexpr int kLiveKT = 2;
+template <bool TB>
+__global__ __launch_bounds__(512, 1) void p32_live_rows_kernel(KernelArgs ka) {
+  constexpr int BK = kP32BK, KT = kLiveKT;
+  using HA = P32Half<true>;
+  using HB = P32Half<TB>;
+  constexpr int AIMG = 32 * BK;                  // rows 0 .. 31 of a k-contiguous half image
+  constexpr int TILE = AIMG + 2 * HB::FLOATS;    // one K-tile: A | B columns 0 .. 127 | 128 .. 255
+  constexpr int NB = KT * 2 * (HB::FLOATS / 4) / 512;   // B units per thread and stage
+  static_assert(KT * (AIMG / 4) <= 512 && NB * 512 == KT * 2 * (HB::FLOATS / 4), "staging must divide evenly");
+  __shared__ __attribute__((aligned(16))) float smem[2 * KT * TILE];
+  const GemmDesc& d = ka.d;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int t = blockIdx.x;
+  int tm, tn;
+  tile_of(t, ka.tiles_m, ka.tiles_n, ka.group_m, tm, tn);
+  const int64_t m0 = (int64_t)tm * 256, m1 = min(m0 + 256, d.M), n0 = (int64_t)tn * 256;
+  // the tile's live rows: d.live_first + j d.live_stride for j in [j0, j0 + nlive)
+  const int64_t j0 = m0 <= d.live_first ? 0 : (m0 - d.live_first + d.live_stride - 1) / d.live_stride;
+  if (m1 <= d.live_first || j0 >= d.live_count) return;
+  const int64_t j1 = min(d.live_count - 1, (m1 - 1 - d.live_first) / d.live_stride);
+  const int nlive = (int)min((int64_t)32, j1 - j0 + 1);
+  if (nlive <= 0) return;
+  // the cuts of the tile's runs, in K-tiles from the tile's first (at most 3 runs)
+  const int64_t total = (int64_t)ka.tiles * ka.sk_ki, t0 = (int64_t)t * ka.sk_ki;
+  const int w0 = sk_owner(t0, total, ka.sk_wgs), w1 = sk_owner(t0 + ka.sk_ki - 1, total, ka.sk_wgs);
+  const int cut1 = w1 > w0 ? (int)(sk_begin(w0 + 1, total, ka.sk_wgs) - t0) : -1;
+  const int cut2 = w1 > w0 + 1 ? (int)(sk_begin(w0 + 2, total, ka.sk_wgs) - t0) : -1;
+
+  v4f ra, rb[NB];
+  const v4f zero4 = v4f{0.f, 0.f, 0.f, 0.f};
+  auto load_stage = [&](int st) {
+    if (tid < KT * (AIMG / 4)) {
+      int row, kk;
+      HA::unit(tid % (AIMG / 4), row, kk);
+      const int64_t k = ((int64_t)st * KT + tid / (AIMG / 4)) * BK + kk;   // K % 4 == 0: a unit is wholly below K or not
+      ra = row < nlive && k < d.K ? ld4(d.A + (d.live_first + (j0 + row) * d.live_stride) * d.lda + k) : zero4;
+    }
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      const int e = tid + 512 * i, u = e % (HB::FLOATS / 4), half = (e / (HB::FLOATS / 4)) & 1;
+      int row, kk;
+      HB::unit(u, row, kk);
+      const int64_t k = ((int64_t)st * KT + e / (2 * (HB::FLOATS / 4))) * BK + kk, n = n0 + half * 128 + row;
+      const bool ok = n < d.N && k < d.K;    // N % 4 == 0 when B is row-contiguous
+      rb[i] = ok ? ld4(TB ? d.B + n * d.ldb + k : d.B + k * d.ldb + n) : zero4;
+    }
+  };
+  auto store_stage = [&](int buf) {
+    float* S = smem + buf * (KT * TILE);
+    if (tid < KT * (AIMG / 4)) st4(S + (tid / (AIMG / 4)) * TILE + (tid % (AIMG / 4)) * 4, ra);
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      const int e = tid + 512 * i;
+      st4(S + (e / (2 * (HB::FLOATS / 4))) * TILE + AIMG + (e % (2 * (HB::FLOATS / 4))) * 4, rb[i]);
+    }
+  };
+
+  f32x16 acc[1][1], sum;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[0][0][r] = sum[r] = 0.f;
+  int nrun = 0;
+  const int bh = wave >> 2, c0 = (wave & 3) * 32;
+  const int nstage = (ka.sk_ki + KT - 1) / KT;
+  load_stage(0);
+  store_stage(0);
+  __syncthreads();
+  for (int st = 0; st < nstage; ++st) {
+    if (st + 1 < nstage) load_stage(st + 1);
+    const float* S = smem + (st & 1) * (KT * TILE);
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) {
+      const int g = st * KT + kt;
+      if (g >= ka.sk_ki) break;
+      if (g == cut1 || g == cut2) {   // a run ends: its partial sum joins the earlier runs', the next starts from zero
+        sum = nrun ? sum + acc[0][0] : acc[0][0];
+        ++nrun;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[0][0][r] = 0.f;
+      }
+#pragma unroll
+      for (int q = 0; q < BK / 8; ++q) {
+        const v4f fa[1] = {HA::frag(S + kt * TILE, 0, q, lane)};
+        const v4f fb[1] = {HB::frag(S + kt * TILE + AIMG + bh * HB::FLOATS, c0, q, lane)};
+        p32_mma_block(fa, fb, acc);
+      }
+    }
+    if (st + 1 < nstage) store_stage((st + 1) & 1);   // that buffer was last read before the previous barrier
+    __syncthreads();
+  }
+  const f32x16 out = nrun ? sum + acc[0][0] : acc[0][0];
+  const int64_t col = n0 + bh * 128 + c0 + (lane & 31);
+  if (col >= d.N) return;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int i = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    if (i < nlive) d.C[(d.live_first + (j0 + i) * d.live_stride) * d.ldc + col] = out[r];
   }
 }
 
@@ -2194,6 +2320,65 @@ bool gemm_f32_p32_split(const GemmDesc& d, int* splits, int64_t* kchunk) {
   return true;
 }
 
+bool gemm_klive_enabled() {
+  static const bool on = [] {
+    const char* v = getenv("SRK_GEMM_KLIVE");
+    return !(v && *v) || atoi(v) != 0;
+  }();
+  return on;
+}
+
+namespace {
+// The plan of gemm_f32(d) -- kernel, grid, cuts and scratch untouched -- with the clip of d.k_live on top: live_ki
+// for the kernels, the flops of the K-tiles that run.  False when d is not a case of gemm_f32_klive (gemm.h).
+bool klive_plan(const GemmDesc& d, GemmPlan& p) {
+  if (d.k_live <= 0 || d.k_live % kP32BK != 0 || d.k_live >= d.K || d.live_count < 1 || d.live_first < 0 ||
+      d.live_stride < 8 || d.live_count > d.M || d.live_first + (d.live_count - 1) * d.live_stride >= d.M)
+    return false;
+  if (d.ta || d.batch != 1 || d.alpha != 1.f || d.beta != 0.f || d.bias_mode != 0 || d.rowsum || d.A16 || d.B16) return false;
+  if (gemm_plan(d, p) != SRK_OK || p.family != kFamP32 || !p.streamk || p.prec != kPrecF32) return false;
+  p.ka.live_ki = (int)(d.k_live / kP32BK);
+  p.flops = 2.0 * (double)d.M * (double)d.N * (double)d.k_live;
+  return true;
+}
+}  // namespace
+
+bool gemm_f32_klive_ok(const GemmDesc& d) {
+  GemmPlan p;
+  return klive_plan(d, p);
+}
+
+int gemm_f32_klive(const GemmDesc& d, hipStream_t s) {
+  GemmPlan p;
+  SRK_REQUIRE(klive_plan(d, p), SRK_ERR_INVALID,
+              "gemm_klive: needs the fp32 stream-K gemm_p32_kernel plan (A not transposed, batch 1, alpha 1, beta 0, no bias, "
+              "no row sums), k_live a multiple of %d in (0, K), live rows below M at a stride >= 8", kP32BK);
+  float* scratch = nullptr;
+  if (int rc = g_scratch.get(plan_scratch(p), &scratch)) return rc;
+  const KernelArgs ka = plan_args(p, d, scratch);
+  {
+    ProfScope prof(p.name, s, p.flops);
+    prof.bytes(p.bytes - 4.0 * (double)d.M * (double)(d.K - d.k_live));
+    if (prof.on()) {
+      char detail[96];
+      gemm_plan_detail(p, d, detail);
+      prof.detail("%s klive %lld", detail, (long long)d.k_live);
+    }
+    hipLaunchKernelGGL(p.kernel, p.grid, p.block, 0, s, ka);
+    hipLaunchKernelGGL(sk_fixup_kernel, dim3((unsigned)ka.tiles * kSkFixupSlices), dim3(256), 0, s, ka);
+    SRK_CHECK_HIP(hipGetLastError());
+  }
+  // the live rows over the full K: 32 rows x 256 columns per tile, whatever the tile holds
+  ProfScope prof(p.name, s, 2.0 * 32 * 256 * (double)ka.tiles * (double)d.K);
+  if (prof.on())
+    prof.detail("p32_live_rows_kernel<N%c> %lldx%lldx%lld rows %lld", d.tb ? 'T' : 'N', (long long)d.M, (long long)d.N,
+                (long long)d.K, (long long)d.live_count);
+  if (d.tb) hipLaunchKernelGGL(p32_live_rows_kernel<true>, dim3((unsigned)ka.tiles), dim3(512), 0, s, ka);
+  else hipLaunchKernelGGL(p32_live_rows_kernel<false>, dim3((unsigned)ka.tiles), dim3(512), 0, s, ka);
+  SRK_CHECK_HIP(hipGetLastError());
+  return SRK_OK;
+}
+
 int gemm_f32_group(const GemmDesc* ds, int n, hipStream_t s) {
   SRK_REQUIRE(ds && n >= 1 && n <= kGemmGroupMax, SRK_ERR_INVALID, "gemm_group: 1 .. %d members", kGemmGroupMax);
   GemmPlan plans[kGemmGroupMax];
@@ -2389,6 +2574,64 @@ extern "C" int srk_gemm_pack_plan(int64_t K, int64_t slab, int64_t first, int64_
   }
   *n_slabs = p.nslabs;
   *packed_slab = p.pslab;
+  return SRK_OK;
+  SRK_API_END
+}
+
+// gemm_f32_klive on raw pointers (tests): op(A) = A, op(B) = B, alpha 1, beta 0.
+extern "C" int srk_gemm_f32_klive(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B,
+                                  int64_t ldb, float* C, int64_t ldc, int64_t k_live, int64_t first, int64_t stride,
+                                  int64_t count, void* stream) {
+  SRK_API_BEGIN
+  srk::GemmDesc d;
+  d.M = M; d.N = N; d.K = K;
+  d.A = A; d.lda = lda;
+  d.B = B; d.ldb = ldb;
+  d.C = C; d.ldc = ldc;
+  d.k_live = k_live; d.live_first = first; d.live_stride = stride; d.live_count = count;
+  return srk::gemm_f32_klive(d, srk::as_stream(stream));
+  SRK_API_END
+}
+
+// What gemm_f32_klive keeps of the stream-K plan of an (M, N, K) product with packed operands, host only: read back
+// through sk_begin / sk_owner / sk_live, the functions the kernels run.
+extern "C" int srk_gemm_klive_plan(int64_t M, int64_t N, int64_t K, int64_t k_live, int64_t first, int64_t stride,
+                                   int64_t count, float beta, int bias_mode, int64_t* kept, int64_t kept_cap,
+                                   int64_t* live_runs, int64_t runs_cap, int64_t* tiles, int64_t* ktiles,
+                                   int64_t* wgs) {
+  SRK_API_BEGIN
+  SRK_REQUIRE(kept && live_runs && tiles && ktiles && wgs && kept_cap >= 0 && runs_cap >= 0, SRK_ERR_INVALID,
+              "gemm_klive_plan: null pointer");
+  srk::GemmDesc d;   // addresses are inspected for alignment and nullness only
+  d.M = M; d.N = N; d.K = K;
+  d.A = reinterpret_cast<const float*>(uintptr_t(256)); d.lda = K;
+  d.B = reinterpret_cast<const float*>(uintptr_t(256)); d.ldb = N;
+  d.C = reinterpret_cast<float*>(uintptr_t(256)); d.ldc = N;
+  d.beta = beta;
+  d.bias_mode = bias_mode; d.bias = bias_mode ? reinterpret_cast<const float*>(uintptr_t(256)) : nullptr;
+  d.k_live = k_live; d.live_first = first; d.live_stride = stride; d.live_count = count;
+  srk::GemmPlan p;
+  SRK_REQUIRE(srk::klive_plan(d, p), SRK_ERR_INVALID, "gemm_klive_plan: not a case of gemm_f32_klive");
+  const srk::KernelArgs& ka = p.ka;
+  SRK_REQUIRE(kept_cap >= ka.sk_wgs && runs_cap >= ka.tiles, SRK_ERR_INVALID,
+              "gemm_klive_plan: need room for %d workgroups and %d tiles", ka.sk_wgs, ka.tiles);
+  const int64_t total = (int64_t)ka.tiles * ka.sk_ki, live = srk::sk_live(ka);
+  for (int w = 0; w < ka.sk_wgs; ++w) {   // the segments of run w, as gemm_p32_body walks them
+    kept[w] = 0;
+    const int64_t end = srk::sk_begin(w + 1, total, ka.sk_wgs);
+    for (int64_t it = srk::sk_begin(w, total, ka.sk_wgs); it < end;) {
+      const int64_t t0 = it / ka.sk_ki * ka.sk_ki, kt_end = std::min(live, end - t0);
+      if (it - t0 < live) kept[w] += kt_end - (it - t0);
+      it = t0 + ka.sk_ki;
+    }
+  }
+  for (int t = 0; t < ka.tiles; ++t) {
+    const int64_t t0 = (int64_t)t * ka.sk_ki;
+    live_runs[t] = srk::sk_owner(t0 + live - 1, total, ka.sk_wgs) - srk::sk_owner(t0, total, ka.sk_wgs) + 1;
+  }
+  *tiles = ka.tiles;
+  *ktiles = ka.sk_ki;
+  *wgs = ka.sk_wgs;
   return SRK_OK;
   SRK_API_END
 }

@@ -808,7 +808,8 @@ int srk_gru_layer_bwd(const float* x, int64_t B, int64_t T, int64_t in, int64_t 
 // zero everywhere (the live step has h_prev = 0: its dgh sits in dgh_edge[1]) and dW_hh[1] = 0.  Modes 1 and 2 issue
 // only the GEMM work that is not identically zero; modes 2 and 3 replace the reverse recurrence by its one cell
 // (rev_cell_bwd_kernel), leaving dgh[1] (and in mode 2 the reverse dgi rows t < T-1) unwritten and unread.  Mode 3
-// zero-fills those dgi rows and keeps the full dW_ih / dx GEMMs: every result then has the full layer's bits.
+// zero-fills those dgi rows and keeps the full dW_ih / dx GEMMs: every result then has the full layer's bits (the
+// grouped dW launch and the clipped dx below keep those bits without reading the zeros, and then the fill goes).
 static int layer_bwd(const float* x, const void* x16_in, int64_t B, int64_t T, int64_t in, int64_t H,
                      const float* w_ih, const float* w_hh, const float* y, const float* ws_fwd, const float* dy,
                      const float* dy_last, const GruPath& path, int top_last, float* dx, float* dw_ih, float* dw_hh,
@@ -847,6 +848,45 @@ static int layer_bwd(const float* x, const void* x16_in, int64_t B, int64_t T, i
     m_y = {nullptr, u16(ws_fwd + F.y16)};
   }
   int rc;
+  const float beta = accumulate ? 1.f : 0.f;   // autograd .grad accumulation in the GEMM epilogues
+  // Mode 3, decided before the recurrence (its zero fill depends on both).  Grouped (last-step
+  // top layer): the full dW_ih GEMM multiplies the reverse half's BT - B zero rows, and the forward dW_hh planned
+  // as the two-direction launch fills half of the CUs.  Both keep their bits as parts: the dW_ih forward half on the
+  // full GEMM's kernel and K split, the reverse half with its all-zero 8-deep k blocks deleted slab by slab
+  // (PackPlan), the dW_hh as before; the three share one launch.  dx_klive: the full dx GEMM, stream-K, without the
+  // K-tiles of the reverse half (gemm_f32_klive), its B live rows (b, T-1) completed over the full K.
+  bool grouped = false;
+  GemmDesc full, hh;   // the one dW_ih GEMM of the ungrouped path | the two-direction dW_hh launch
+  srk::PackPlan pp;
+  if (top_last == 3 && !h16 && T >= 16 && srk::gemm_group_enabled()) {
+    full.M = 6 * H; full.N = ld; full.K = BT;
+    full.A = dgi; full.lda = 6 * H; full.ta = true;
+    full.B = m_x.f; full.ldb = ld;
+    full.C = pad ? dwpad : dw_ih; full.ldc = ld; full.beta = pad ? 0.f : beta;
+    full.rowsum = db_ih; full.rowsum_beta = beta;
+    hh.M = 3 * H; hh.N = H; hh.K = BT - 1;
+    hh.ta = true; hh.lda = 3 * H; hh.ldb = 2 * H;
+    hh.A = dgh + 3 * H; hh.B = y;
+    hh.C = dw_hh; hh.ldc = H; hh.beta = beta;
+    hh.batch = 2; hh.sA = BT * 3 * H - 3 * H; hh.sB = 3 * H; hh.sC = 3 * H * H;
+    hh.rowsum = db_hh; hh.rowsum_beta = beta; hh.sRS = 3 * H;
+    int splits = 0;
+    int64_t kchunk = 0;
+    grouped = srk::gemm_f32_p32_split(full, &splits, &kchunk) && splits > 1 && srk::g_opt_gru_dwhh_batched &&
+              srk::gemm_f32_batched_rowsum_ok(hh) && srk::pack_plan(BT, kchunk, T - 1, T, B, pp) == SRK_OK &&
+              pp.nslabs == splits;
+  }
+  GemmDesc gdx;   // dx[BT, in] = dgi[BT, 6H] * W_ih_cat[6H, in]
+  gdx.M = BT; gdx.N = ld; gdx.K = (top_last == 1 || top_last == 2) ? 3 * H : 6 * H;
+  set_a(gdx, m_dgi); gdx.lda = 6 * H;
+  set_b(gdx, m_w); gdx.ldb = ld;
+  gdx.C = pad ? dxpad : dx; gdx.ldc = ld;
+  bool dx_klive = false;
+  if (dx && top_last == 3 && !h16 && srk::gemm_klive_enabled()) {
+    gdx.k_live = 3 * H; gdx.live_first = T - 1; gdx.live_stride = T; gdx.live_count = B;
+    dx_klive = srk::gemm_f32_klive_ok(gdx);
+    if (!dx_klive) gdx.k_live = 0;
+  }
   // the recurrent weight gradient accumulated inside the recurrence kernel (partials per row group)
   const int dw_parts = h16 ? path.bwd.dw_parts : 0;
   if (path.persistent) {
@@ -878,8 +918,11 @@ static int layer_bwd(const float* x, const void* x16_in, int64_t B, int64_t T, i
         return rc;
       }
     }
-    // top_last == 3: the full dW_ih / dx GEMMs below read whole dgi rows: the reverse columns' true value, zero
-    if (top_last == 3 && (rc = srk::launch256(srk::zero_cols_kernel, BT * 3 * H / 4, s, dgi, BT, 3 * H, 3 * H, 6 * H)))
+    // top_last == 3: the full dW_ih / dx GEMMs below read whole dgi rows: the reverse columns' true value, zero.
+    // Nothing reads them when dW_ih goes through the group (its packing copies the live rows only) and dx through
+    // gemm_f32_klive.
+    const bool rev_unread = grouped && (!dx || dx_klive);
+    if (top_last == 3 && !rev_unread && (rc = srk::launch256(srk::zero_cols_kernel, BT * 3 * H / 4, s, dgi, BT, 3 * H, 3 * H, 6 * H)))
       return rc;
     if (top_last >= 2 && (rc = srk::launch256(srk::rev_cell_bwd_kernel, B * H, s, gates, dy_last, B, T, H, dgi, dgh_edge)))
       return rc;
@@ -898,62 +941,35 @@ static int layer_bwd(const float* x, const void* x16_in, int64_t B, int64_t T, i
     SRK_CHECK_HIP(hipGetLastError());
   }
 
-  const float beta = accumulate ? 1.f : 0.f;   // autograd .grad accumulation in the GEMM epilogues
   // fp32: the bias gradients are fused row sums of the GEMMs' A operands (16-bit: from the kernel's partials, above)
   const bool sums = !h16;
   // modes 1 and 2: the reverse direction's dgi taken as its B live rows (b, T-1), lda = T 6H; mode 3 keeps the full
   // dW_ih / dx GEMMs (their sums' order, so their bits) and drops only the reverse dW_hh
   const bool rev_last = top_last == 1 || top_last == 2;
   const Mat m_dgi_rev = m_dgi.at((T - 1) * 6 * H + 3 * H);
-  // Mode 3, grouped (last-step top layer): the full dW_ih GEMM multiplies the reverse half's
-  // BT - B zero rows, and the forward dW_hh planned as the two-direction launch fills half of the CUs.  Both keep
-  // their bits as parts: the dW_ih forward half on the full GEMM's kernel and K split, the reverse half with its
-  // all-zero 8-deep k blocks deleted slab by slab (PackPlan), the dW_hh as before; the three share one launch.
-  bool grouped = false;
-  if (top_last == 3 && !h16 && T >= 16 && srk::gemm_group_enabled()) {
-    GemmDesc full;   // the one dW_ih GEMM of the ungrouped path
-    full.M = 6 * H; full.N = ld; full.K = BT;
-    full.A = dgi; full.lda = 6 * H; full.ta = true;
-    full.B = m_x.f; full.ldb = ld;
-    full.C = pad ? dwpad : dw_ih; full.ldc = ld; full.beta = pad ? 0.f : beta;
-    full.rowsum = db_ih; full.rowsum_beta = beta;
-    GemmDesc hh;     // the two-direction dW_hh launch the forward-only one is planned as
-    hh.M = 3 * H; hh.N = H; hh.K = BT - 1;
-    hh.ta = true; hh.lda = 3 * H; hh.ldb = 2 * H;
-    hh.A = dgh + 3 * H; hh.B = y;
-    hh.C = dw_hh; hh.ldc = H; hh.beta = beta;
-    hh.batch = 2; hh.sA = BT * 3 * H - 3 * H; hh.sB = 3 * H; hh.sC = 3 * H * H;
-    hh.rowsum = db_hh; hh.rowsum_beta = beta; hh.sRS = 3 * H;
-    int splits = 0;
-    int64_t kchunk = 0;
-    srk::PackPlan pp;
-    if (srk::gemm_f32_p32_split(full, &splits, &kchunk) && splits > 1 && srk::g_opt_gru_dwhh_batched &&
-        srk::gemm_f32_batched_rowsum_ok(hh) && srk::pack_plan(BT, kchunk, T - 1, T, B, pp) == SRK_OK &&
-        pp.nslabs == splits) {
-      grouped = true;
-      const int64_t rows = pp.nslabs * pp.pslab;
-      float* packed = nullptr;   // A' [rows][3H] | B' [rows][ld]
-      if ((rc = srk::g_gs.get((size_t)rows * (3 * H + ld), &packed))) return rc;
-      if ((rc = srk::gemm_pack_rows(pp, dgi + 3 * H, 6 * H, 3 * H, m_x.f, ld, ld, packed, packed + rows * 3 * H, s)))
-        return rc;
-      GemmDesc m[3];
-      m[0] = full;   // the forward half: rows 0 .. 3H of the full GEMM
-      m[0].M = 3 * H; m[0].plan_M = 6 * H;
-      m[1] = hh;     // the forward direction of the two-direction launch
-      m[1].batch = 1; m[1].plan_batch = 2;
-      m[2] = m[0];   // the reverse half over the packed K
-      m[2].K = rows; m[2].pin_splits = (int)pp.nslabs; m[2].pin_kchunk = pp.pslab;
-      m[2].A = packed; m[2].lda = 3 * H;
-      m[2].B = packed + rows * 3 * H;
-      m[2].C = full.C + 3 * H * ld;
-      m[2].rowsum = db_ih + 3 * H;
-      if ((rc = srk::gemm_f32_group(m, 3, s))) return rc;
-      if (pad && (rc = srk::launch256(srk::unpad_cols_kernel, 6 * H * in, s, dwpad, 6 * H, ld, dw_ih, in, accumulate)))
-        return rc;
-      if (!accumulate) {   // dW_hh[1] = 0; db_hh[1] = the column sums of dgh_edge[1] below
-        SRK_CHECK_HIP(hipMemsetAsync(dw_hh + 3 * H * H, 0, sizeof(float) * 3 * H * H, s));
-        SRK_CHECK_HIP(hipMemsetAsync(db_hh + 3 * H, 0, sizeof(float) * 3 * H, s));
-      }
+  if (grouped) {
+    const int64_t rows = pp.nslabs * pp.pslab;
+    float* packed = nullptr;   // A' [rows][3H] | B' [rows][ld]
+    if ((rc = srk::g_gs.get((size_t)rows * (3 * H + ld), &packed))) return rc;
+    if ((rc = srk::gemm_pack_rows(pp, dgi + 3 * H, 6 * H, 3 * H, m_x.f, ld, ld, packed, packed + rows * 3 * H, s)))
+      return rc;
+    GemmDesc m[3];
+    m[0] = full;   // the forward half: rows 0 .. 3H of the full GEMM
+    m[0].M = 3 * H; m[0].plan_M = 6 * H;
+    m[1] = hh;     // the forward direction of the two-direction launch
+    m[1].batch = 1; m[1].plan_batch = 2;
+    m[2] = m[0];   // the reverse half over the packed K
+    m[2].K = rows; m[2].pin_splits = (int)pp.nslabs; m[2].pin_kchunk = pp.pslab;
+    m[2].A = packed; m[2].lda = 3 * H;
+    m[2].B = packed + rows * 3 * H;
+    m[2].C = full.C + 3 * H * ld;
+    m[2].rowsum = db_ih + 3 * H;
+    if ((rc = srk::gemm_f32_group(m, 3, s))) return rc;
+    if (pad && (rc = srk::launch256(srk::unpad_cols_kernel, 6 * H * in, s, dwpad, 6 * H, ld, dw_ih, in, accumulate)))
+      return rc;
+    if (!accumulate) {   // dW_hh[1] = 0; db_hh[1] = the column sums of dgh_edge[1] below
+      SRK_CHECK_HIP(hipMemsetAsync(dw_hh + 3 * H * H, 0, sizeof(float) * 3 * H * H, s));
+      SRK_CHECK_HIP(hipMemsetAsync(db_hh + 3 * H, 0, sizeof(float) * 3 * H, s));
     }
   }
   if (!grouped) {
@@ -1034,12 +1050,8 @@ static int layer_bwd(const float* x, const void* x16_in, int64_t B, int64_t T, i
     } else if (!h16 && pad) {
       if ((rc = srk::pad_cols(w_ih, 6 * H, in, wpad, s))) return rc;
     }
-    GemmDesc g;
-    g.M = BT; g.N = ld; g.K = rev_last ? 3 * H : 6 * H;
-    set_a(g, m_dgi); g.lda = 6 * H;
-    set_b(g, m_w); g.ldb = ld;
-    g.C = pad ? dxpad : dx; g.ldc = ld;
-    if ((rc = srk::gemm_f32(g, s))) return rc;
+    GemmDesc g = gdx;
+    if ((rc = dx_klive ? srk::gemm_f32_klive(g, s) : srk::gemm_f32(g, s))) return rc;
     if (rev_last) {   // rows (b, T-1) += dgi_rev_last * W_ih[1]
       g.M = B;
       set_a(g, m_dgi_rev); g.lda = T * 6 * H;
