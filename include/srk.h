@@ -699,6 +699,54 @@ int srk_specaug_apply(const float* x, int64_t B, int64_t T, int64_t F, int time_
 int srk_specaug_draw(uint64_t* state, int64_t B, int64_t T, int64_t F, int W, int NF, int f_max, int NT, int t_max,
                      int32_t* params_out, void* stream);
 
+/* ---------------------------------------------------------------- mixup and label smoothing
+ * Mixup (Zhang et al., ICLR 2018) on the PCM a training step receives, and the soft-target cross-entropy that goes
+ * with it (features.mixup_draw / mixup, nn.CrossEntropyLoss(label_smoothing)(.., mix=); no reference counterpart).
+ * Clip b is mixed with clip partner[b] at weight lam[b]; both arrays are ordinary device arrays (int32 [B],
+ * float [B]) that the draw fills and the apply and the loss read.
+ *
+ * srk_mixup_draw draws them on the device (one launch, graph-replayable) from the state and hash of
+ * srk_uniform_f64_state: state = uint64[2] {base, counter}, seed = base + 0xD1B54A32D192ED03 * counter,
+ * z_i = the splitmix64 finaliser of seed + 0x9E3779B97F4A7C15 * (i + 1), u_i = (z_i >> 11) * 2^-53.
+ *  - lam[b] ~ Beta(alpha, alpha) by Joehnk's method, at most SRK_MIXUP_TRIALS trials: trial k takes
+ *    U = u_{(32 b + k) 2} and V = u_{(32 b + k) 2 + 1}, X = pow(U, 1 / alpha), Y = pow(V, 1 / alpha), S = X + Y
+ *    (all double; at alpha == 1, X = U and Y = V exactly); the first k with 0 < S <= 1 is accepted: l = X / S, then
+ *    l = max(l, 1 - l) (a clip dominates its own mix), lam[b] = (float)l.  No trial accepted: lam[b] = 1.
+ *  - one rotation for the batch: r = 1 + (((z_j >> 32) * (B - 1)) >> 32) with j = 64 B, partner[b] = (b + r) % B:
+ *    a bijection without a fixed point.  B == 1: partner[0] = 0 and lam[0] = 1.
+ * Then the call advances state[1] by one.  Acceptance is 1/2 per trial at alpha = 1 and higher below it, and pow
+ * cannot underflow to a denormal down to alpha = 0.1: the domain is 0.1 <= alpha <= 1.
+ * The host refuses, SRK_ERR_INVALID with "mixup" in srk_last_error(): B < 1, B > 2^24, alpha outside [0.1, 1] or not
+ * finite, a null pointer.  Profiler category "mixup_draw".
+ *
+ * srk_mixup_apply: x, out fp32 [B][n] contiguous, out of place,
+ *   out[b][i] = fl(lam_b * x[b][i]) + fl(w_b * x[partner_b][i]),   w_b = fl(1 - lam_b)
+ * (fp32, four roundings, no contraction).  Any values are accepted (self, duplicates, lam anywhere in [0, 1]); they
+ * live on the device (no host check): the kernel validates a row before it reads through it, and a row whose
+ * partner is outside [0, B) or whose lam is not in [0, 1] (NaN included) gets NaN in its whole output row; no
+ * out-of-range address is formed and the other rows are unaffected.  One launch, two reads and one write per
+ * element (12 B n bytes), 16-byte accesses when n % 4 == 0 and x, out are 16-byte aligned (a scalar path
+ * otherwise).  The host refuses, "mixup" in srk_last_error(): out overlapping x, B < 1, n < 1 (or above 2^31 - 1, or
+ * more than 2^31 - 1 workgroups), a null pointer.  Profiler category "mixup" (one record per launch, 12 B n bytes).
+ *
+ * srk_cross_entropy_mix is srk_cross_entropy on the soft target of a mixed and / or smoothed batch.  partner and lam
+ * are both NULL (label smoothing alone: lam_b = 1) or both given; with q_b = labels[partner_b] and eps = smoothing,
+ *   t[b][c] = (1 - eps) (lam_b [c == y_b] + (1 - lam_b) [c == q_b]) + eps / C
+ * (torch's label_smoothing on the mixed target), loss[0] = mean_b(logsumexp(z_b) - sum_c t[b][c] z[b][c]), dlogits
+ * (nullable) = (softmax - t) / B.  ws: B + 1 floats; the same two launches and the same deterministic mean as
+ * srk_cross_entropy, and with partner == lam == NULL and smoothing == 0 the same bits in loss and dlogits.  An
+ * out-of-range label (a row's own or its partner's), a partner outside [0, B) or a lam not in [0, 1] makes that
+ * row's loss, and so the loss, NaN.  The host refuses, "cross_entropy" in srk_last_error(): smoothing outside
+ * [0, 1) or not finite, a shape outside srk_cross_entropy's domain (or B >= 2^31), exactly one of partner / lam
+ * NULL, a null pointer.                                                                                          */
+#define SRK_MIXUP_TRIALS 32
+int srk_mixup_draw(uint64_t* state, int64_t B, double alpha, int32_t* partner, float* lam, void* stream);
+int srk_mixup_apply(const float* x, int64_t B, int64_t n, const int32_t* partner, const float* lam, float* out,
+                    void* stream);
+int srk_cross_entropy_mix(const float* logits, const int64_t* labels, const int32_t* partner, const float* lam,
+                          int64_t B, int64_t C, float smoothing, float* loss, float* dlogits, float* ws,
+                          void* stream);
+
 /* ---------------------------------------------------------------- diagnostics (tests only)
  * Directed checks of two instruction patterns (csrc/diag.hip; tests/test_diag_gpu.py):
  * srk_diag_acc_store: the row-staged data gradient's epilogue (raw buffer stores of 32x32 MFMA

@@ -146,6 +146,9 @@ _SIGS = {
     "srk_avgpool_nhwc_bwd": [_P, _I64, _I64, _I64, _P, _P],
     "srk_specaug_apply": [_P, _I64, _I64, _I64, _I, _P, _I, _I, _I, _F, _P, _P],
     "srk_specaug_draw": [_P, _I64, _I64, _I64, _I, _I, _I, _I, _I, _P, _P],
+    "srk_mixup_draw": [_P, _I64, _D, _P, _P, _P],
+    "srk_mixup_apply": [_P, _I64, _I64, _P, _P, _P, _P],
+    "srk_cross_entropy_mix": [_P, _P, _P, _P, _I64, _I64, _F, _P, _P, _P, _P],
 }
 _RESTYPE = {"srk_last_error": ctypes.c_char_p, "srk_spin_timeouts": ctypes.c_int64, "srk_scratch_generation": ctypes.c_int64, "srk_gru_workspace_floats": ctypes.c_int64, "srk_gru_y16_offset": ctypes.c_int64,
             "srk_gru_top_last_workspace_floats": ctypes.c_int64,

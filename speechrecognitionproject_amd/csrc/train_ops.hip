@@ -1,5 +1,6 @@
 // K7/K8: the small training-step kernels around the acoustic models.
 //  * cross-entropy (mean over the batch) forward + backward  — nn.CrossEntropyLoss, training.py:73,87
+//    and the same on the soft target of a mixed / label-smoothed batch (srk_cross_entropy_mix)
 //  * Adam (beta1, beta2, eps; no weight decay, no amsgrad)     — torch.optim.Adam, training.py:74,91
 //    over one flat fp32 parameter buffer (one launch for the whole model)
 //  * inverted dropout with an explicit mask                     — nn.Dropout(), model_fbanks_cnn.py:79,98
@@ -38,6 +39,67 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
   if (lane == 0) loss_rows[b] = lse - row[lab];
   if (dx)
     for (int c = lane; c < C; c += 64) dx[(size_t)b * C + c] = (expf(row[c] - lse) - (c == lab ? 1.f : 0.f)) * scale;
+}
+
+// ce_rows_kernel on a soft target (include/srk.h srk_cross_entropy_mix): with q = labels[partner_b], w = 1 - lam_b,
+//   t_c = (1 - eps) (lam_b [c == y] + w [c == q]) + eps / C,   loss_rows[b] = lse - sum_c t_c x_c,
+//   dx = (softmax(x_b) - t) * scale.
+// partner == lam == nullptr: q = y, lam_b = 1.  A weight of exactly 0 drops its term and eps == 0 drops the
+// smoothing sum, so without a mix and with eps == 0 every value is ce_rows_kernel's, bit for bit.  A row is
+// validated before anything is read through its partner or labels.
+__global__ __launch_bounds__(256) void ce_mix_rows_kernel(const float* __restrict__ x,
+                                                          const int64_t* __restrict__ labels,
+                                                          const int32_t* __restrict__ partner,
+                                                          const float* __restrict__ lam, int B, int C, float eps,
+                                                          float scale, float* __restrict__ loss_rows,
+                                                          float* __restrict__ dx, int* __restrict__ bad) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const float* row = x + (size_t)b * C;
+  const int64_t lab = labels[b];
+  int64_t q = lab;
+  float l = 1.f;
+  bool ok = lab >= 0 && lab < C;
+  if (partner) {
+    const int p = partner[b];
+    l = lam[b];
+    ok = ok && p >= 0 && p < B && l >= 0.f && l <= 1.f;   // NaN fails both comparisons
+    if (ok) {
+      q = labels[p];
+      ok = q >= 0 && q < C;
+    }
+  }
+  if (!ok) {   // the loss becomes NaN (loud), flag set
+    if (lane == 0) {
+      atomicExch(bad, 1);
+      loss_rows[b] = NAN;
+    }
+    return;
+  }
+  const float w = 1.f - l;
+  float m = -INFINITY;
+  for (int c = lane; c < C; c += 64) m = fmaxf(m, row[c]);
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  float s = 0.f;
+  for (int c = lane; c < C; c += 64) s += expf(row[c] - m);
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  const float lse = m + logf(s);
+  float tz = (l != 0.f ? l * row[lab] : 0.f) + (w != 0.f ? w * row[q] : 0.f);
+  if (eps != 0.f) {
+    float sz = 0.f;
+    for (int c = lane; c < C; c += 64) sz += row[c];
+    for (int o = 32; o > 0; o >>= 1) sz += __shfl_xor(sz, o, 64);
+    tz = (1.f - eps) * tz + (eps / (float)C) * sz;
+  }
+  if (lane == 0) loss_rows[b] = lse - tz;
+  if (dx) {
+    const float keep = 1.f - eps, floor_t = eps / (float)C;
+    for (int c = lane; c < C; c += 64) {
+      const float t = keep * ((c == lab ? l : 0.f) + (c == q ? w : 0.f)) + floor_t;
+      dx[(size_t)b * C + c] = (expf(row[c] - lse) - t) * scale;
+    }
+  }
 }
 
 // Deterministic mean of the per-row losses (one workgroup).
@@ -252,6 +314,28 @@ int srk_cross_entropy(const float* logits, const int64_t* labels, int64_t B, int
   SRK_CHECK_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
   hipLaunchKernelGGL(srk::ce_rows_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, logits, labels, (int)B,
                      (int)C, 1.0f / (float)B, ws, dlogits, bad);
+  hipLaunchKernelGGL(srk::mean_kernel, dim3(1), dim3(256), 0, s, ws, (int)B, loss);
+  SRK_CHECK_HIP(hipGetLastError());
+  return SRK_OK;
+  SRK_API_END
+}
+
+int srk_cross_entropy_mix(const float* logits, const int64_t* labels, const int32_t* partner, const float* lam,
+                          int64_t B, int64_t C, float smoothing, float* loss, float* dlogits, float* ws,
+                          void* stream) {
+  SRK_API_BEGIN
+  SRK_REQUIRE(B > 0 && B < (int64_t(1) << 31) && C > 0 && C <= 4096, SRK_ERR_INVALID, "cross_entropy_mix: bad shape");
+  SRK_REQUIRE(smoothing >= 0.f && smoothing < 1.f, SRK_ERR_INVALID,
+              "cross_entropy_mix: smoothing must be in [0, 1), got %g", (double)smoothing);
+  SRK_REQUIRE((partner == nullptr) == (lam == nullptr), SRK_ERR_INVALID,
+              "cross_entropy_mix: partner and lam are both given or both NULL");
+  SRK_REQUIRE(logits && labels && loss && ws, SRK_ERR_INVALID, "cross_entropy_mix: null pointer");
+  hipStream_t s = srk::as_stream(stream);
+  // ws: B floats of per-row loss, then one int error flag (as srk_cross_entropy)
+  int* bad = reinterpret_cast<int*>(ws + B);
+  SRK_CHECK_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
+  hipLaunchKernelGGL(srk::ce_mix_rows_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, logits, labels, partner,
+                     lam, (int)B, (int)C, smoothing, 1.0f / (float)B, ws, dlogits, bad);
   hipLaunchKernelGGL(srk::mean_kernel, dim3(1), dim3(256), 0, s, ws, (int)B, loss);
   SRK_CHECK_HIP(hipGetLastError());
   return SRK_OK;

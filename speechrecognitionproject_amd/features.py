@@ -318,6 +318,108 @@ def spec_augment(x, params, policy, time_major=True, out=None):
     return out
 
 
+# ---------------------------------------------------------------- mixup (srk_mixup_draw / srk_mixup_apply)
+MIXUP_ALPHA = (0.1, 1.0)      # srk_mixup_draw's domain of alpha
+MIXUP_MAX_CLIPS = 1 << 24
+
+# Mixup draws: device index -> uint64[2] {base seed, call counter}, a state of its own exactly as _SPECAUG_STATE is
+# (another salt): turning mixup on moves neither the dropout masks, the VTLP factors nor the SpecAugment draws.
+_MIXUP_STATE = {}
+_MIXUP_SALT = 0x4D49585550213F21   # "MIXUP!?!"
+
+
+def _mixup_state(device):
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    st = _MIXUP_STATE.get(idx)
+    if st is None:
+        seed = torch.cuda.default_generators[idx].initial_seed()
+        dist = torch.distributed
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        base = ((seed * 0x9E3779B97F4A7C15) ^ (rank * 0xC2B2AE3D27D4EB4F) ^ _MIXUP_SALT) & _MASK63
+        st = torch.tensor([base, 0], dtype=torch.int64, device=torch.device("cuda", idx))
+        _MIXUP_STATE[idx] = st
+    return st
+
+
+def mixup_reseed(seed, device=None):
+    """Reset the mixup draw state of ``device`` (default: the current one): base = ``seed``, counter = 0.  An
+    existing state is rewritten where it is (on the current stream), so a captured graph that draws from it goes
+    on from the new seed."""
+    require_gpu()
+    idx = torch.cuda.current_device() if device is None else torch.device(device).index
+    idx = torch.cuda.current_device() if idx is None else idx
+    fresh = torch.tensor([int(seed) & _MASK63, 0], dtype=torch.int64)
+    if idx in _MIXUP_STATE:
+        _MIXUP_STATE[idx].copy_(fresh)
+    else:
+        _MIXUP_STATE[idx] = fresh.to(torch.device("cuda", idx))
+
+
+def mixup_state(device=None):
+    """(base, counter) of the mixup draw state (synchronizes; for tests and logs)."""
+    require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    base, counter = _mixup_state(dev).tolist()
+    return base, counter
+
+
+def check_mixup_alpha(alpha):
+    """``alpha`` as a float inside srk_mixup_draw's domain, or ValueError (pure Python: no GPU needed)."""
+    a = float(alpha)
+    if not MIXUP_ALPHA[0] <= a <= MIXUP_ALPHA[1]:      # NaN fails both comparisons
+        raise ValueError("mixup: alpha must be in [%g, %g], got %r" % (MIXUP_ALPHA + (alpha,)))
+    return a
+
+
+def mixup_draw(B, alpha, out=None):
+    """The mixup of B clips: (partner int32 [B], lam float32 [B]) on the current device (srk_mixup_draw: one
+    rotation of the batch, so every clip is some clip's partner and none its own, and lam ~ Beta(alpha, alpha)
+    folded into [0.5, 1]).  ``out``: a (partner, lam) pair to fill.  Draw k of a process hashes (base, k, clip,
+    trial) on the device and the kernel itself advances k, so an eager call and a replay of a captured one are the
+    same arithmetic."""
+    require_gpu()
+    alpha = check_mixup_alpha(alpha)
+    if out is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+        partner = torch.empty(B, device=dev, dtype=torch.int32)
+        lam = torch.empty(B, device=dev, dtype=torch.float32)
+    else:
+        partner, lam = out
+        for t, dt in ((partner, torch.int32), (lam, torch.float32)):
+            if t.dtype != dt or tuple(t.shape) != (B,) or not t.is_contiguous() or t.device.type != "cuda":
+                raise SrkError("mixup_draw: out must be (int32, float32) contiguous device tensors of %d elements" % B)
+        if partner.device != lam.device:
+            raise SrkError("mixup_draw: partner and lam must be on one device")
+    call("srk_mixup_draw", ptr(_mixup_state(partner.device)), B, alpha, ptr(partner), ptr(lam), stream_ptr())
+    return partner, lam
+
+
+def mixup(x, partner, lam, out=None):
+    """Mixup (srk_mixup_apply) of a batch: x float32 [B, ...] contiguous on the device, out[b] = lam[b] x[b] +
+    (1 - lam[b]) x[partner[b]] in fp32; partner int32 [B] and lam float32 [B] from ``mixup_draw``, or any sequences
+    (uploaded).  Out of place: ``out`` must not overlap x.  A row whose partner is outside [0, B) or whose lam is
+    outside [0, 1] comes back all NaN (the values live on the device: no host check)."""
+    require_gpu()
+    if not torch.is_tensor(x) or x.dim() < 1 or x.dtype != torch.float32 or x.device.type != "cuda" \
+            or not x.is_contiguous():
+        raise SrkError("mixup: x must be a contiguous float32 device tensor [B, ...]")
+    B = x.shape[0]
+    partner = torch.as_tensor(partner, dtype=torch.int32) if not torch.is_tensor(partner) else partner
+    lam = torch.as_tensor(lam, dtype=torch.float32) if not torch.is_tensor(lam) else lam
+    if partner.dtype != torch.int32 or lam.dtype != torch.float32 or tuple(partner.shape) != (B,) \
+            or tuple(lam.shape) != (B,):
+        raise SrkError("mixup: partner must be int32 and lam float32, both of shape (%d,), got %s %s and %s %s"
+                       % (B, partner.dtype, tuple(partner.shape), lam.dtype, tuple(lam.shape)))
+    partner, lam = partner.to(x.device).contiguous(), lam.to(x.device).contiguous()
+    out = torch.empty_like(x) if out is None else out
+    if out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise SrkError("mixup: out must match x (shape, float32, contiguous, same device)")
+    if x.numel() == 0:
+        return out
+    call("srk_mixup_apply", ptr(x), B, x.numel() // B, ptr(partner), ptr(lam), ptr(out), stream_ptr())
+    return out
+
+
 def mfcc(pcm, time_major=False, out=None):
     """K1 MFCC+deltas: [B, 39, 51], or [B, 51, 39] if ``time_major`` (model_mfcc_bgru.py:11-19,34)."""
     x = as_device_pcm(pcm, keep_int16=True)

@@ -488,12 +488,54 @@ class _CrossEntropyFn(torch.autograd.Function):
         return dlogits * g, None
 
 
-class CrossEntropyLoss(tnn.Module):
-    """Drop-in for ``nn.CrossEntropyLoss()`` (mean reduction), training.py:73."""
+class _CrossEntropyMixFn(torch.autograd.Function):
+    """srk_cross_entropy_mix: the loss on the soft target of a mixed (partner, lam) and / or smoothed batch."""
 
-    def forward(self, logits, labels):
+    @staticmethod
+    def forward(ctx, logits, labels, partner, lam, smoothing):
+        logits = logits.contiguous()
+        _check_cuda(logits)
+        B, C = logits.shape
+        labels = labels.to(device=logits.device, dtype=torch.int64).contiguous()
+        if partner is not None:
+            partner = torch.as_tensor(partner).to(device=logits.device, dtype=torch.int32).contiguous()
+            lam = torch.as_tensor(lam).to(device=logits.device, dtype=torch.float32).contiguous()
+            if tuple(partner.shape) != (B,) or tuple(lam.shape) != (B,):
+                raise _lib.SrkError("CrossEntropyLoss: mix = (partner, lam) must hold one value per row (%d), got %s "
+                                    "and %s" % (B, tuple(partner.shape), tuple(lam.shape)))
+        loss = torch.empty((), device=logits.device)
+        dlogits = torch.empty_like(logits) if ctx.needs_input_grad[0] else None
+        ws = torch.empty(B + 1, device=logits.device)
+        call("srk_cross_entropy_mix", ptr(logits), ptr(labels), _optr(partner), _optr(lam), B, C, float(smoothing),
+             ptr(loss), _optr(dlogits), ptr(ws), stream_ptr())
+        ctx.save_for_backward(dlogits)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlogits,) = ctx.saved_tensors
+        return dlogits * g, None, None, None, None
+
+
+class CrossEntropyLoss(tnn.Module):
+    """Drop-in for ``nn.CrossEntropyLoss()`` (mean reduction), training.py:73.  ``label_smoothing`` is torch's
+    (0 <= eps < 1); ``forward(.., mix=(partner, lam))`` takes the loss on a mixed batch's soft target, row b's
+    target being lam[b] of its own label and 1 - lam[b] of row partner[b]'s (features.mixup_draw), smoothed after.
+    Without either it is srk_cross_entropy as before."""
+
+    def __init__(self, label_smoothing=0.0):
+        super().__init__()
+        eps = float(label_smoothing)
+        if not 0.0 <= eps < 1.0:
+            raise ValueError("CrossEntropyLoss: label_smoothing must be in [0, 1), got %r" % (label_smoothing,))
+        self.label_smoothing = eps
+
+    def forward(self, logits, labels, mix=None):
         require_gpu()
-        return _CrossEntropyFn.apply(logits, labels)
+        if mix is None and self.label_smoothing == 0.0:
+            return _CrossEntropyFn.apply(logits, labels)
+        partner, lam = (None, None) if mix is None else mix
+        return _CrossEntropyMixFn.apply(logits, labels, partner, lam, self.label_smoothing)
 
 
 # ----------------------------------------------------------------------------- 16-bit operand copies

@@ -34,6 +34,12 @@ linearly around it, NF masks of up to FMAX features and NT masks of up to TMAX f
 (``--specaug-fill zero``: with 0).  One draw launch and one in-place launch per step (srk_specaug_draw / _apply);
 the draw's state is its own device counter, so the flag moves neither the dropout masks nor the VTLP factors, and a
 replayed step draws what the eager step would have drawn.  Evaluation never augments.
+``--mixup ALPHA`` (0.1..1, every plugin and precision, off by default) mixes each training clip's PCM with another
+clip of its batch, lam ~ Beta(ALPHA, ALPHA) folded into [0.5, 1] and one rotation of the batch as the pairing, both
+drawn on the device (srk_mixup_draw, a counter of its own) and applied in one pass over the PCM (srk_mixup_apply);
+the loss is then taken on the mixed labels.  ``--label-smoothing EPS`` (0 <= EPS < 1, default 0) spreads EPS of the
+target over all classes, torch's convention; either flag routes the loss through srk_cross_entropy_mix.  A short
+last batch is mixed within itself.  Evaluation is untouched.
 """
 import argparse
 import importlib
@@ -46,6 +52,7 @@ from torch.utils.data import DataLoader
 from . import parallel
 from . import _lib
 from ._lib import check_health
+from .features import as_device_pcm, mixup, mixup_draw
 from .nn import CrossEntropyLoss
 from .optim import Adam, FlatParams, LossScaler
 
@@ -108,7 +115,17 @@ def parse(argv=None):
                         "e.g. 5,2,15,2,12 for the 98 x 120 filter banks; off by default" % ', '.join(SPECAUG_SHAPES))
     p.add_argument('--specaug-fill', choices=('mean', 'zero'), default='mean',
                    help="--specaug: what a masked element becomes: its clip's mean (default) or 0")
+    p.add_argument('--mixup', type=float, default=None, metavar='ALPHA',
+                   help="mix each training clip's PCM with another clip of its batch, the weight drawn from "
+                        "Beta(ALPHA, ALPHA) on the device and the loss taken on the mixed labels; 0.1 <= ALPHA <= 1, "
+                        "e.g. 0.4; off by default")
+    p.add_argument('--label-smoothing', type=float, default=0.0, metavar='EPS',
+                   help="spread EPS of each target over all classes (torch's label_smoothing); 0 <= EPS < 1")
     args = p.parse_args(argv)
+    if args.mixup is not None and not 0.1 <= args.mixup <= 1.0:
+        p.error('--mixup needs 0.1 <= ALPHA <= 1, got %r' % args.mixup)
+    if not 0.0 <= args.label_smoothing < 1.0:
+        p.error('--label-smoothing needs 0 <= EPS < 1, got %r' % args.label_smoothing)
     if args.specaug is not None:
         if args.model not in SPECAUG_SHAPES:
             p.error('--specaug applies to --model %s only' % ', '.join(SPECAUG_SHAPES))
@@ -190,7 +207,7 @@ def _train(args):
     cap_group = parallel.capture_group() if (use_graph and world > 1) else None
     reducer = parallel.GradReducer(flat, capture_group=cap_group) if (world > 1 and args.overlap) else None
     scheduler = torch.optim.lr_scheduler.ExponentialLR(optimizer, 0.87)
-    criterion = CrossEntropyLoss()
+    criterion = CrossEntropyLoss(label_smoothing=args.label_smoothing)
     scaler = None
     if args.precision == 'fp16':
         if args.loss_scale == 'dynamic':
@@ -210,8 +227,14 @@ def _train(args):
         optimizer.zero_grad()
         if reducer is not None:
             reducer.begin()
+        mix = None
+        if args.mixup is not None:
+            # on the PCM, before any feature kernel: the same for every plugin; a replayed step replays the draw
+            x = as_device_pcm(x)
+            mix = mixup_draw(x.shape[0], args.mixup)
+            x = mixup(x, *mix)
         outputs = model(x)
-        loss = criterion(outputs, y)
+        loss = criterion(outputs, y, mix=mix)
         (scaler.scale(loss) if scaler is not None else loss).backward()
         if reducer is not None:
             reducer.finish()
