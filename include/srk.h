@@ -546,6 +546,33 @@ int srk_grad_scaler_init(int32_t* scaler, float init_scale, float growth_factor,
  * growth_interval clean steps.                                                                    */
 int srk_adam_step_scaled(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float beta1,
                          float beta2, float eps, int64_t* state, float grad_scale, int32_t* scaler, void* stream);
+/* Floats of workspace srk_adamw_step needs while clipping is on: one partial sum per workgroup of the gradient-norm
+ * pass, whose grid depends on n alone (min(ceil(n / 1024), 1024), at least 1).  0 for n < 0.             */
+int64_t srk_adamw_workspace_floats(int64_t n);
+/* srk_adam_step_state / srk_adam_step_scaled (scaler nullable) with decoupled weight decay, global-norm gradient
+ * clipping and an exponential moving average of the weights, all optional, every per-step value on the device:
+ *   norm    (clipping on, or a scaler) one read of grad: total_norm = sqrt(sum (grad[i] * s)^2), s = grad_scale
+ *           [/ scale], summed in a fixed order (same n and bits in, same bits out; no atomics on floats), and the
+ *           scaler's found_inf raised on a non-finite element (srk_adam_step_scaled's check, in the same read);
+ *   prep    coef = min(1, max_norm / (total_norm + 1e-6)) (torch.nn.utils.clip_grad_norm_); clip_state, 16 B
+ *           on the device {float total_norm, float coef, int32 clipped_steps, int32 0}, is written; clipped_steps
+ *           advances on a step that is not skipped and has coef < 1; the step count advances as in the others;
+ *   update  one pass: a skipped step (scaler overflow) writes nothing; else gg = grad * s * coef; where
+ *           decay_mask marks the element's 64-float chunk (one byte per chunk, ceil(n / 64) bytes; NULL = every
+ *           chunk) param *= 1 - lr * weight_decay (torch.optim.AdamW, lr from state); srk_adam_step_state's
+ *           arithmetic; then ema = ema_decay * ema + (1 - ema_decay) * param where ema (n floats) is given.
+ * max_norm <= 0 or +inf: clipping off (clip_state and ws are not touched and may be NULL); weight_decay == 0: no
+ * decay; ema NULL: no average.  With all three off the result is srk_adam_step_state's (srk_adam_step_scaled's with a
+ * scaler), bit for bit.  ws: srk_adamw_workspace_floats(n) floats, fully written before they are read.
+ * Checked on the host before any device work, SRK_ERR_INVALID with "adamw" and the argument's name in
+ * srk_last_error(): n < 0; state NULL; param / grad / exp_avg / exp_avg_sq NULL with n > 0; param, grad, exp_avg,
+ * exp_avg_sq, ema off 16 bytes, state off 8, scaler / clip_state / ws off 4; weight_decay negative or not finite;
+ * max_norm NaN; clip_state or ws NULL while clipping is on; ema given with ema_decay outside [0, 1) or aliasing
+ * another buffer.                                                                                          */
+int srk_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float beta1,
+                   float beta2, float eps, int64_t* state, float grad_scale, int32_t* scaler, float weight_decay,
+                   const uint8_t* decay_mask, float max_norm, int32_t* clip_state, float* ema, float ema_decay,
+                   float* ws, void* stream);
 /* nn.Dropout(p) training forward: keep[i] = Bernoulli(1-p) from a counter-based hash of
  * (seed, i) (not torch's RNG stream), y = keep ? x / (1-p) : 0.                              */
 int srk_dropout_fwd(const float* x, int64_t n, float p, uint64_t seed, float* y, uint8_t* keep, void* stream);

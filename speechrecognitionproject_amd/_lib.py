@@ -132,6 +132,8 @@ _SIGS = {
     "srk_adam_step_state": [_P, _P, _P, _P, _I64, _F, _F, _F, _P, _F, _P],
     "srk_grad_scaler_init": [_P, _F, _F, _F, _I, _P],
     "srk_adam_step_scaled": [_P, _P, _P, _P, _I64, _F, _F, _F, _P, _F, _P, _P],
+    "srk_adamw_workspace_floats": [_I64],
+    "srk_adamw_step": [_P, _P, _P, _P, _I64, _F, _F, _F, _P, _F, _P, _F, _P, _F, _P, _P, _F, _P, _P],
     "srk_dropout_apply": [_P, _P, _I64, _F, _P, _P],
     "srk_attn_pool_fwd": [_P, _P, _I64, _I64, _I64, _F, _P, _P, _P],
     "srk_attn_pool_bwd": [_P, _P, _P, _P, _I64, _I64, _I64, _F, _P, _P, _P],
@@ -154,7 +156,8 @@ _RESTYPE = {"srk_last_error": ctypes.c_char_p, "srk_spin_timeouts": ctypes.c_int
             "srk_gru_top_last_workspace_floats": ctypes.c_int64,
             "srk_conv2d_workspace_floats": ctypes.c_int64, "srk_conv1_pool_workspace_floats": ctypes.c_int64,
             "srk_pitch_workspace_bytes": ctypes.c_int64, "srk_source_stamp": ctypes.c_char_p,
-            "srk_pcen_workspace_floats": ctypes.c_int64, "srk_dwconv2d_workspace_floats": ctypes.c_int64}
+            "srk_pcen_workspace_floats": ctypes.c_int64, "srk_dwconv2d_workspace_floats": ctypes.c_int64,
+            "srk_adamw_workspace_floats": ctypes.c_int64}
 
 
 class SrkError(RuntimeError):

@@ -260,6 +260,198 @@ __global__ __launch_bounds__(256) void adam_state_kernel(float* __restrict__ p, 
   adam_body(p, g, m, v, n, f[2], b1, b2, eps, f[0], f[1], grad_scale);
 }
 
+// ---- AdamW decay, global-norm clipping and a weight EMA around the same update (include/srk.h srk_adamw_step) ----
+// Clip state on the device: what the norm pass measured and what the update multiplies the gradient by.
+struct ClipState {
+  float total_norm, coef;
+  int32_t clipped_steps, pad;
+};
+
+constexpr int kNormThreads = 256;
+constexpr int kNormMaxBlocks = 1024;
+// The norm pass's grid, a function of n alone (the summation order, and so the bits, follow from it).
+inline int64_t norm_blocks(int64_t n) {
+  return std::max<int64_t>(1, std::min<int64_t>((n + kNormThreads * 4 - 1) / (kNormThreads * 4), kNormMaxBlocks));
+}
+
+// One read of the gradient: part[block] = sum over the block's elements of (g[i] * s)^2 and, with a scaler,
+// found_inf |= any non-finite element (finite_check_kernel's test and atomic).  s = grad_scale [* inv_scale], applied
+// before squaring so loss-scaled gradients cannot overflow the sum.  Fixed order, no floating-point atomics: a lane
+// adds its elements in index order (grid stride 4 * blocks * 256), the 64 lanes fold by xor 32, 16, ... 1 (both
+// partners of a pair compute the same commutative sum), wave 0's lane 0 adds the four wave sums in wave order.
+// NORM = false: the finite check alone (a scaler without clipping), part is not touched.
+template <bool NORM>
+__global__ __launch_bounds__(kNormThreads) void grad_norm_kernel(const float* __restrict__ g, int64_t n,
+                                                                 float grad_scale, ScalerState* __restrict__ sc,
+                                                                 float* __restrict__ part) {
+  __shared__ float wave_sum[kNormThreads / 64];
+  const float s = sc ? grad_scale * sc->inv_scale : grad_scale;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
+  float acc = 0.f;
+  bool bad = false;
+  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
+    if (i + 3 < n) {
+      const float4 v = *reinterpret_cast<const float4*>(g + i);
+      // |x| <= FLT_MAX is false exactly for +-inf and NaN
+      bad |= !(fabsf(v.x) <= FLT_MAX) || !(fabsf(v.y) <= FLT_MAX) || !(fabsf(v.z) <= FLT_MAX) ||
+             !(fabsf(v.w) <= FLT_MAX);
+      if (NORM) {
+        const float a = v.x * s, b = v.y * s, c = v.z * s, d = v.w * s;
+        acc += a * a;
+        acc += b * b;
+        acc += c * c;
+        acc += d * d;
+      }
+    } else {
+      for (int64_t k = i; k < n; ++k) {
+        bad |= !(fabsf(g[k]) <= FLT_MAX);
+        if (NORM) {
+          const float a = g[k] * s;
+          acc += a * a;
+        }
+      }
+    }
+  }
+  if (sc && __ballot(bad) != 0 && (threadIdx.x & 63) == 0) atomicOr(&sc->found_inf, 1);
+  if (NORM) {
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+  }
+}
+
+// adam_prep_kernel plus the clip coefficient, one workgroup: the partials are summed in double in a fixed order
+// (thread t takes t, t + 256, ...; then a halving tree), total_norm = sqrt(sum), coef = min(1, max_norm /
+// (total_norm + 1e-6)) in float as torch.nn.utils.clip_grad_norm_ (a NaN norm gives a NaN coef, as torch's clamp).
+// clip == nullptr: no clipping, the step count alone.
+__global__ __launch_bounds__(256) void adam_prep_clip_kernel(int64_t* __restrict__ state, float beta1, float beta2,
+                                                             const ScalerState* __restrict__ sc,
+                                                             const float* __restrict__ part, int nparts,
+                                                             float max_norm, ClipState* __restrict__ clip) {
+  __shared__ double tree[256];
+  const bool skipped = sc && sc->found_inf;
+  if (clip) {
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += 256) s += (double)part[i];
+    tree[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+      if ((int)threadIdx.x < w) tree[threadIdx.x] += tree[threadIdx.x + w];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      const float total = (float)sqrt(tree[0]);
+      const float c = max_norm / (total + 1e-6f);
+      const float coef = c > 1.f ? 1.f : c;
+      clip->total_norm = total;
+      clip->coef = coef;
+      if (!skipped && coef < 1.f) clip->clipped_steps += 1;
+      clip->pad = 0;
+    }
+  }
+  if (threadIdx.x != 0 || skipped) return;
+  // adam_prep_kernel's lines
+  const int64_t step = state[0] + 1;
+  state[0] = step;
+  float* bc = reinterpret_cast<float*>(state + 1);
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  bc[0] = (float)bc1;
+  bc[1] = (float)sqrt(bc2);
+}
+
+// One element of the extended update.  Every rounding is spelled out (no contraction, explicit fmaf), because with
+// coef == 1, no decay and no EMA the result has to be adam_body's bits, and adam_body as compiled for gfx950 rounds by
+// code path: the float4 body fuses m = fma(1 - b1, gg, b1 m) and v = fma(gg, (1 - b2) gg, b2 v), the scalar tail's
+// pair loop (the tail vectorised by two) fuses m = fma(b1, m, (1 - b1) gg) instead, and the tail's last single
+// element fuses neither sum; all three end in p = fma(-(lr / bc1), m / denom, p).  tests/test_optim_ext_gpu.py holds
+// the two kernels to each other at every tail length.
+enum AdamRounding { kRoundVec4, kRoundPair, kRoundSingle };
+
+template <AdamRounding R>
+__device__ __forceinline__ void adamw_element(float& p, float g, float& m, float& v, float* __restrict__ ema, float gs,
+                                              float kp, float b1, float b2, float c1, float c2, float eps,
+                                              float bc2_sqrt, float step_size, float d) {
+#pragma clang fp contract(off)
+  const float gg = g * gs;
+  const float pd = p * kp;                 // keep == 1.0f gives p back exactly
+  if (R == kRoundVec4) {
+    m = __builtin_fmaf(c1, gg, b1 * m);
+  } else if (R == kRoundPair) {
+    m = __builtin_fmaf(b1, m, c1 * gg);
+  } else {
+    m = b1 * m + c1 * gg;
+  }
+  if (R == kRoundSingle) {
+    v = gg * (c2 * gg) + b2 * v;
+  } else {
+    v = __builtin_fmaf(gg, c2 * gg, b2 * v);
+  }
+  const float denom = sqrtf(v) / bc2_sqrt + eps;
+  p = __builtin_fmaf(-step_size, m / denom, pd);
+  if (ema) *ema = d * *ema + (1.f - d) * p;
+}
+
+// adam_state_kernel with three more operands.  Per element, in this order: a skipped step writes nothing;
+// gg = g * (s * coef) (coef == 1.0f: the float adam_body computes); a chunk marked for decay (one mask byte per 64
+// floats, nullptr = every chunk) has p *= 1 - lr * weight_decay first (torch.optim.AdamW's decoupled form, the factor
+// formed in double as torch forms it on the host); then adam_body's arithmetic; then ema = d * ema + (1 - d) * p_new
+// where an EMA buffer is given.  A float4 never straddles a chunk (i % 4 == 0).
+__global__ __launch_bounds__(256) void adamw_state_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                          float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                          float b1, float b2, float eps,
+                                                          const int64_t* __restrict__ state, float grad_scale,
+                                                          const ScalerState* __restrict__ sc, float weight_decay,
+                                                          const uint8_t* __restrict__ mask,
+                                                          const ClipState* __restrict__ clip, float* __restrict__ ema,
+                                                          float ema_decay) {
+#pragma clang fp contract(off)
+  if (sc) {
+    if (sc->found_inf) return;
+    grad_scale *= sc->inv_scale;
+  }
+  const float* f = reinterpret_cast<const float*>(state + 1);   // bc1, sqrt(bc2), lr
+  const float bc1 = f[0], bc2_sqrt = f[1], lr = f[2];
+  // one gradient factor, s * coef: with coef == 1.0f it is s itself
+  const float gs = grad_scale * (clip ? clip->coef : 1.f);
+  const float keep = (float)(1.0 - (double)lr * (double)weight_decay);
+  const bool decay = weight_decay != 0.f;
+  const float c1 = 1.f - b1, c2 = 1.f - b2, step_size = lr / bc1;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
+  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
+    if (i + 3 < n) {
+      const float kp = (decay && (!mask || mask[i >> 6])) ? keep : 1.f;
+      float4 gv = *reinterpret_cast<const float4*>(g + i);
+      float4 mv = *reinterpret_cast<float4*>(m + i);
+      float4 vv = *reinterpret_cast<float4*>(v + i);
+      float4 pv = *reinterpret_cast<float4*>(p + i);
+      float4 ev = ema ? *reinterpret_cast<float4*>(ema + i) : float4{0.f, 0.f, 0.f, 0.f};
+      float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x; float* pp = &pv.x; float* ep = &ev.x;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        adamw_element<kRoundVec4>(pp[k], gp[k], mp[k], vp[k], ema ? ep + k : nullptr, gs, kp, b1, b2, c1, c2, eps,
+                                  bc2_sqrt, step_size, ema_decay);
+      *reinterpret_cast<float4*>(m + i) = mv;
+      *reinterpret_cast<float4*>(v + i) = vv;
+      *reinterpret_cast<float4*>(p + i) = pv;
+      if (ema) *reinterpret_cast<float4*>(ema + i) = ev;
+    } else {
+      // adam_body's tail as compiled: pairs first, then a last single element
+      const int64_t pairs_end = i + ((n - i) & ~(int64_t)1);
+      for (int64_t k = i; k < n; ++k) {
+        const float kp = (decay && (!mask || mask[k >> 6])) ? keep : 1.f;
+        if (k < pairs_end)
+          adamw_element<kRoundPair>(p[k], g[k], m[k], v[k], ema ? ema + k : nullptr, gs, kp, b1, b2, c1, c2, eps,
+                                    bc2_sqrt, step_size, ema_decay);
+        else
+          adamw_element<kRoundSingle>(p[k], g[k], m[k], v[k], ema ? ema + k : nullptr, gs, kp, b1, b2, c1, c2, eps,
+                                      bc2_sqrt, step_size, ema_decay);
+      }
+    }
+  }
+}
+
 // Dropout whose seed lives on the device ([base, counter]): the mask of call k hashes base + k, and
 // the counter advances behind the mask kernel — so a captured graph draws a fresh mask per replay.
 __global__ void dropout_state_kernel(const float* __restrict__ x, int64_t n, float p, float scale,
@@ -421,6 +613,66 @@ int srk_adam_step_scaled(float* param, const float* grad, float* exp_avg, float*
                        exp_avg_sq, n, beta1, beta2, eps, state, grad_scale, (const srk::ScalerState*)sc);
   }
   hipLaunchKernelGGL(srk::scaler_update_kernel, dim3(1), dim3(1), 0, s, sc);
+  SRK_CHECK_HIP(hipGetLastError());
+  return SRK_OK;
+  SRK_API_END
+}
+
+int64_t srk_adamw_workspace_floats(int64_t n) { return n < 0 ? 0 : srk::norm_blocks(n); }
+
+int srk_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float beta1,
+                   float beta2, float eps, int64_t* state, float grad_scale, int32_t* scaler, float weight_decay,
+                   const uint8_t* decay_mask, float max_norm, int32_t* clip_state, float* ema, float ema_decay,
+                   float* ws, void* stream) {
+  SRK_API_BEGIN
+  SRK_REQUIRE(n >= 0, SRK_ERR_INVALID, "adamw: n must be >= 0, got %lld", (long long)n);
+  SRK_REQUIRE(state, SRK_ERR_INVALID, "adamw: state is null");
+  SRK_REQUIRE(n == 0 || (param && grad && exp_avg && exp_avg_sq), SRK_ERR_INVALID,
+              "adamw: param, grad, exp_avg and exp_avg_sq must not be null");
+  const struct { const char* name; const void* p; unsigned align; } ptrs[] = {
+      {"param", param, 16}, {"grad", grad, 16}, {"exp_avg", exp_avg, 16}, {"exp_avg_sq", exp_avg_sq, 16},
+      {"ema", ema, 16}, {"state", state, 8}, {"scaler", scaler, 4}, {"clip_state", clip_state, 4}, {"ws", ws, 4}};
+  for (const auto& a : ptrs)
+    SRK_REQUIRE((uintptr_t)a.p % a.align == 0, SRK_ERR_INVALID, "adamw: %s must be %u-byte aligned", a.name, a.align);
+  SRK_REQUIRE(weight_decay >= 0.f && std::isfinite(weight_decay), SRK_ERR_INVALID,
+              "adamw: weight_decay must be finite and >= 0, got %g", (double)weight_decay);
+  SRK_REQUIRE(!std::isnan(max_norm), SRK_ERR_INVALID, "adamw: max_norm is NaN");
+  const bool clip_on = max_norm > 0.f && std::isfinite(max_norm);   // <= 0 or +inf: clipping is off
+  SRK_REQUIRE(!clip_on || clip_state, SRK_ERR_INVALID, "adamw: clip_state is null while clipping is on (max_norm %g)",
+              (double)max_norm);
+  SRK_REQUIRE(!clip_on || ws, SRK_ERR_INVALID,
+              "adamw: ws is null while clipping is on (max_norm %g): srk_adamw_workspace_floats(n) floats",
+              (double)max_norm);
+  SRK_REQUIRE(ema == nullptr || (ema_decay >= 0.f && ema_decay < 1.f), SRK_ERR_INVALID,
+              "adamw: ema_decay must be in [0, 1) with an ema buffer, got %g", (double)ema_decay);
+  SRK_REQUIRE(ema == nullptr || (ema != param && ema != exp_avg && ema != exp_avg_sq && ema != grad), SRK_ERR_INVALID,
+              "adamw: ema must be a buffer of its own");
+  if (n == 0 && !scaler) return SRK_OK;   // as srk_adam_step_state
+  hipStream_t s = srk::as_stream(stream);
+  auto* sc = reinterpret_cast<srk::ScalerState*>(scaler);
+  auto* clip = clip_on ? reinterpret_cast<srk::ClipState*>(clip_state) : nullptr;
+  const int64_t nparts = clip_on && n > 0 ? srk::norm_blocks(n) : 0;
+  if (n > 0 && clip_on) {
+    srk::ProfScope prof("grad_norm", s, 4.0 * (double)n);
+    hipLaunchKernelGGL(srk::grad_norm_kernel<true>, dim3((unsigned)nparts), dim3(srk::kNormThreads), 0, s, grad, n,
+                       grad_scale, sc, ws);
+  } else if (n > 0 && sc) {
+    srk::ProfScope prof("grad_check", s, 4.0 * (double)n);
+    hipLaunchKernelGGL(srk::grad_norm_kernel<false>, dim3((unsigned)srk::norm_blocks(n)), dim3(srk::kNormThreads), 0,
+                       s, grad, n, grad_scale, sc, (float*)nullptr);
+  }
+  hipLaunchKernelGGL(srk::adam_prep_clip_kernel, dim3(1), dim3(256), 0, s, state, beta1, beta2,
+                     (const srk::ScalerState*)sc, (const float*)ws, (int)nparts, max_norm, clip);
+  if (n > 0) {
+    const int nt = 256;
+    const int64_t blocks = std::min<int64_t>((n + nt * 4 - 1) / (nt * 4), 256 * 8);   // adam_state_kernel's grid
+    // p, g, m, v read + p, m, v written; ema read + written; one mask byte per 64 floats
+    srk::ProfScope prof("adamw", s, (28.0 + (ema ? 8.0 : 0.0) + (decay_mask ? 1.0 / 64.0 : 0.0)) * (double)n);
+    hipLaunchKernelGGL(srk::adamw_state_kernel, dim3((unsigned)blocks), dim3(nt), 0, s, param, grad, exp_avg,
+                       exp_avg_sq, n, beta1, beta2, eps, state, grad_scale, (const srk::ScalerState*)sc, weight_decay,
+                       decay_mask, (const srk::ClipState*)clip, ema, ema_decay);
+  }
+  if (sc) hipLaunchKernelGGL(srk::scaler_update_kernel, dim3(1), dim3(1), 0, s, sc);
   SRK_CHECK_HIP(hipGetLastError());
   return SRK_OK;
   SRK_API_END

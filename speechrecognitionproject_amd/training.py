@@ -40,8 +40,14 @@ drawn on the device (srk_mixup_draw, a counter of its own) and applied in one pa
 the loss is then taken on the mixed labels.  ``--label-smoothing EPS`` (0 <= EPS < 1, default 0) spreads EPS of the
 target over all classes, torch's convention; either flag routes the loss through srk_cross_entropy_mix.  A short
 last batch is mixed within itself.  Evaluation is untouched.
+``--weight-decay WD`` (decoupled, torch.optim.AdamW's, on weights of two and more dimensions), ``--clip-grad-norm
+MAXNORM`` (torch.nn.utils.clip_grad_norm_ over all parameters, after the all-reduce, on the averaged gradient) and
+``--ema DECAY`` (an exponential moving average of the weights; the per-epoch accuracy lines and ``--save-model`` then
+use the averaged weights) extend the optimizer step on the device (optim.Adam, srk_adamw_step): every plugin and
+precision, replayed and eager steps alike, all off by default.
 """
 import argparse
+import contextlib
 import importlib
 import os
 import time
@@ -121,7 +127,24 @@ def parse(argv=None):
                         "e.g. 0.4; off by default")
     p.add_argument('--label-smoothing', type=float, default=0.0, metavar='EPS',
                    help="spread EPS of each target over all classes (torch's label_smoothing); 0 <= EPS < 1")
+    p.add_argument('--weight-decay', type=float, default=0.0, metavar='WD',
+                   help="decoupled weight decay (torch.optim.AdamW's) on every weight of two and more dimensions; "
+                        "biases and normalisation parameters are left alone; WD >= 0, off by default")
+    p.add_argument('--clip-grad-norm', type=float, default=None, metavar='MAXNORM',
+                   help="scale the gradient down to a global 2-norm of MAXNORM where it is larger "
+                        "(torch.nn.utils.clip_grad_norm_); MAXNORM >= 0, 0 or absent = off")
+    p.add_argument('--ema', type=float, default=None, metavar='DECAY',
+                   help="keep an exponential moving average of the weights, ema = DECAY ema + (1 - DECAY) w after "
+                        "every step, and evaluate and save it instead of the raw weights; 0 <= DECAY < 1, e.g. 0.999")
     args = p.parse_args(argv)
+    if not 0.0 <= args.weight_decay < float('inf'):
+        p.error('--weight-decay needs a finite WD >= 0, got %r' % args.weight_decay)
+    if args.clip_grad_norm is not None and not 0.0 <= args.clip_grad_norm < float('inf'):
+        p.error('--clip-grad-norm needs a finite MAXNORM >= 0, got %r' % args.clip_grad_norm)
+    if args.clip_grad_norm == 0.0:
+        args.clip_grad_norm = None
+    if args.ema is not None and not 0.0 <= args.ema < 1.0:
+        p.error('--ema needs 0 <= DECAY < 1, got %r' % args.ema)
     if args.mixup is not None and not 0.1 <= args.mixup <= 1.0:
         p.error('--mixup needs 0.1 <= ALPHA <= 1, got %r' % args.mixup)
     if not 0.0 <= args.label_smoothing < 1.0:
@@ -152,10 +175,11 @@ def parse(argv=None):
 
 
 def main(argv=None):
+    """Train as the command line says; returns {'model', 'optimizer'} as they stand after the last step."""
     args = parse(argv)
     saved = _lib.matmul_precision()
     try:
-        _train(args)
+        return _train(args)
     finally:
         _lib.set_matmul_precision(saved)      # process-wide: give the caller back its own mode
         _lib.set_option("conv_fwd_fp32", 0)
@@ -196,7 +220,10 @@ def _train(args):
         from .nn import convert_sync_batchnorm
         model = convert_sync_batchnorm(model)
     flat = FlatParams(model.parameters())
-    optimizer = Adam(model.parameters(), lr=lr, flat=flat)
+    optimizer = Adam(model.parameters(), lr=lr, flat=flat, weight_decay=args.weight_decay,
+                     max_grad_norm=args.clip_grad_norm, ema_decay=args.ema)
+    # evaluation and the checkpoint read the averaged weights where there is an average
+    averaged = optimizer.ema_weights if args.ema is not None else contextlib.nullcontext
     optimizer.grad_scale = 1.0 / world
     parallel.broadcast_flat(flat)
     # data-parallel steps are captured whole (the bucketed collectives included, on the capture-only
@@ -338,8 +365,9 @@ def _train(args):
                 flush()
         flush()
         if not args.no_eval and rank == 0:
-            mod.accuracy(model, valset, os.path.join(args.output_path, 'val_' + key + '.txt'), 4)
-            mod.accuracy(model, data, os.path.join(args.output_path, 'train_' + key + '.txt'), 4)
+            with averaged():
+                mod.accuracy(model, valset, os.path.join(args.output_path, 'val_' + key + '.txt'), 4)
+                mod.accuracy(model, data, os.path.join(args.output_path, 'train_' + key + '.txt'), 4)
             check_health(sync=True)
         if world > 1:
             parallel.barrier()    # the other ranks wait here (long timeout), not inside a collective
@@ -348,13 +376,18 @@ def _train(args):
             data.resample_unknown_class()
     if args.save_model and rank == 0:
         os.makedirs(os.path.join(args.output_path, 'models'), exist_ok=True)
-        torch.save(model.state_dict(), os.path.join(args.output_path, 'models', 'model_' + key + '.ckpt'))
+        with averaged():
+            torch.save(model.state_dict(), os.path.join(args.output_path, 'models', 'model_' + key + '.ckpt'))
     if scaler is not None and rank == 0:
         print('fp16 steps skipped (inf/NaN gradients): %d, final loss scale %g' % (scaler.overflows(), scaler.get_scale()))
+    if args.clip_grad_norm is not None and rank == 0:
+        print('steps with a clipped gradient (norm above %g): %d, last norm %g'
+              % (args.clip_grad_norm, optimizer.clipped_steps(), optimizer.last_grad_norm()))
     if rank == 0:
         print('key  ', key)
         print('time  ', time.time() - start)
         print('epochs  ', epoch)
+    return {'model': model, 'optimizer': optimizer}
 
 
 if __name__ == '__main__':
