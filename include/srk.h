@@ -454,7 +454,10 @@ int srk_maxpool_nhwc_bwd(const float* x, const float* dy, int64_t N, int64_t H, 
  * training = 1: batch statistics (biased variance), running stats updated in place with
  * `momentum` (unbiased variance), as nn.BatchNorm1d; training = 0: running statistics.
  * save_mean / save_invstd [C] are written for the backward.  Backward takes the forward's y (for
- * the ReLU mask) and writes dx (nullable), dgamma, dbeta and dresidual (nullable).            */
+ * the ReLU mask) and writes dx (nullable), dgamma, dbeta and dresidual (nullable).
+ * Special values follow torch: ReLU keeps NaN (y = v <= 0 ? 0 : v, so -0.0 gives +0.0 and +inf stays);
+ * gradient passes where !(y <= 0), i.e. y > 0 or NaN.  A non-finite x in training mode makes its
+ * channel's statistics, running statistics and outputs non-finite, as nn.BatchNorm1d's.          */
 int srk_batchnorm_fwd(const float* x, int64_t M, int64_t C, const float* gamma, const float* beta, float eps,
                       float momentum, int training, float* running_mean, float* running_var, const float* residual,
                       int relu, float* y, float* save_mean, float* save_invstd, void* stream);
@@ -481,8 +484,8 @@ int srk_batchnorm_bwd16_acc(const float* x, const float* y, const float* dy, int
                             const float* gamma, const float* save_mean, const float* save_invstd, int training,
                             int relu, float* dx, void* dx16, int* dx16_written, float* dgamma, float* dbeta,
                             float* dresidual, float* dgamma_acc, float* dbeta_acc, void* stream);
-/* The ReLU as bits: with relu set, fwd16_mask also writes relu_mask (M*C/4 bytes; byte i holds bit e = y[4i+e] > 0,
- * nullable), and bwd16_mask takes that mask in place of y (y may then be null) — the backward's two reads of the
+/* The ReLU as bits: with relu set, fwd16_mask also writes relu_mask (M*C/4 bytes; byte i holds bit e = !(y[4i+e] <= 0):
+ * y > 0 or NaN, nullable), and bwd16_mask takes that mask in place of y (y may then be null) — the backward's two reads of the
  * ReLU pattern are 1/16 of y's bytes.  Otherwise as fwd16 / bwd16_acc, whose results they equal bit for bit. */
 int srk_batchnorm_fwd16_mask(const float* x, int64_t M, int64_t C, const float* gamma, const float* beta, float eps,
                              float momentum, int training, float* running_mean, float* running_var,

@@ -278,8 +278,10 @@ __global__ void bn_apply_kernel(const float* __restrict__ x, int64_t M, int C, c
     unsigned bits = 0;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      bits |= (v[e] > 0.f ? 1u : 0u) << e;   // y > 0 exactly (NaN -> 0, as the ReLU below)
-      v[e] = v[e] > 0.f ? v[e] : 0.f;
+      // torch.relu's rule: NaN stays NaN (and -0.0 becomes +0.0), and the gradient passes wherever !(y <= 0),
+      // so the bit is y > 0 or NaN: what the y-reading backward decides from y itself
+      bits |= (v[e] <= 0.f ? 0u : 1u) << e;
+      v[e] = v[e] <= 0.f ? 0.f : v[e];
     }
     if (mask) mask[i4] = (uint8_t)bits;
   }
