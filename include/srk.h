@@ -522,17 +522,22 @@ int srk_batchnorm_bwd_dx(const float* x, const float* y, const float* dy, int64_
 /* ---------------------------------------------------------------- K7/K8: step ops
  * Cross-entropy, mean over the batch (nn.CrossEntropyLoss, training.py:73,87):
  * loss[0] = mean_b(logsumexp(logits_b) - logits_b[label_b]); dlogits (nullable) =
- * (softmax - onehot) / B.  ws: B + 1 floats.  An out-of-range label makes the loss NaN.     */
+ * (softmax - onehot) / B.  ws: B + 1 floats.  An out-of-range label makes the loss NaN.  It is
+ * srk_cross_entropy_mix's kernel without a mix and without smoothing, under its own error texts. */
 int srk_cross_entropy(const float* logits, const int64_t* labels, int64_t B, int64_t C, float* loss,
                       float* dlogits, float* ws, void* stream);
 /* torch.optim.Adam step (no weight decay / amsgrad) over n contiguous floats (training.py:74,91);
- * step is the 1-based step count after increment; grad is multiplied by grad_scale first.   */
+ * step is the 1-based step count after increment; grad is multiplied by grad_scale first.  The
+ * four Adam entries run one update (srk_adamw_step says what it computes); this one takes lr and
+ * the step count from the host.                                                              */
 int srk_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                   float beta1, float beta2, float eps, int64_t step, float grad_scale, void* stream);
 /* The same step with its per-step values on the device, so a captured HIP graph can replay it:
  * state is a 4-int64 (32-B) device buffer — int64 step, then floats bc1, sqrt(bc2), lr, 0.  The
  * caller writes lr (float, byte offset 16); the call advances the step and derives the bias
- * corrections on the device (double precision, as srk_adam_step's host side).                    */
+ * corrections on the device (double precision, as srk_adam_step's host side).  It is
+ * srk_adamw_step without a scaler and with decay, clipping and the EMA off; n == 0 returns before
+ * any launch.                                                                                     */
 int srk_adam_step_state(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float beta1,
                         float beta2, float eps, int64_t* state, float grad_scale, void* stream);
 /* Loss scaling for 16-bit training (torch.cuda.amp.GradScaler semantics, on the device so a
@@ -542,7 +547,9 @@ int srk_adam_step_state(float* param, const float* grad, float* exp_avg, float* 
  * backward.  No reference counterpart: the reference trains fp32 only (training.py:85-91).       */
 int srk_grad_scaler_init(int32_t* scaler, float init_scale, float growth_factor, float backoff_factor,
                          int growth_interval, void* stream);
-/* srk_adam_step_state on loss-scaled gradients: one pass flags any non-finite gradient element;
+/* The step on loss-scaled gradients (srk_adamw_step with a scaler and decay, clipping and the EMA
+ * off; with n == 0 the step count and the scaler still advance): one pass flags any non-finite
+ * gradient element;
  * if one is found the step is SKIPPED (parameters, moments and the step count unchanged), the
  * overflow counter (word 7) advances and a dynamic scale backs off; otherwise the gradients are
  * multiplied by grad_scale / scale inside the update and a dynamic scale grows after
@@ -552,21 +559,24 @@ int srk_adam_step_scaled(float* param, const float* grad, float* exp_avg, float*
 /* Floats of workspace srk_adamw_step needs while clipping is on: one partial sum per workgroup of the gradient-norm
  * pass, whose grid depends on n alone (min(ceil(n / 1024), 1024), at least 1).  0 for n < 0.             */
 int64_t srk_adamw_workspace_floats(int64_t n);
-/* srk_adam_step_state / srk_adam_step_scaled (scaler nullable) with decoupled weight decay, global-norm gradient
- * clipping and an exponential moving average of the weights, all optional, every per-step value on the device:
+/* The Adam step with every per-step value on the device: a loss scaler (nullable), decoupled weight decay,
+ * global-norm gradient clipping and an exponential moving average of the weights, all optional:
  *   norm    (clipping on, or a scaler) one read of grad: total_norm = sqrt(sum (grad[i] * s)^2), s = grad_scale
  *           [/ scale], summed in a fixed order (same n and bits in, same bits out; no atomics on floats), and the
- *           scaler's found_inf raised on a non-finite element (srk_adam_step_scaled's check, in the same read);
+ *           scaler's found_inf raised on a non-finite element in the same read (a scaler without clipping: that
+ *           check alone);
  *   prep    coef = min(1, max_norm / (total_norm + 1e-6)) (torch.nn.utils.clip_grad_norm_); clip_state, 16 B
  *           on the device {float total_norm, float coef, int32 clipped_steps, int32 0}, is written; clipped_steps
  *           advances on a step that is not skipped and has coef < 1; the step count advances as in the others;
  *   update  one pass: a skipped step (scaler overflow) writes nothing; else gg = grad * s * coef; where
  *           decay_mask marks the element's 64-float chunk (one byte per chunk, ceil(n / 64) bytes; NULL = every
- *           chunk) param *= 1 - lr * weight_decay (torch.optim.AdamW, lr from state); srk_adam_step_state's
- *           arithmetic; then ema = ema_decay * ema + (1 - ema_decay) * param where ema (n floats) is given.
+ *           chunk) param *= 1 - lr * weight_decay (torch.optim.AdamW, lr from state); then torch.optim.Adam's
+ *           update, m = b1 m + (1 - b1) gg, v = b2 v + (1 - b2) gg^2, param -= (lr / bc1) m / (sqrt(v) / sqrt(bc2)
+ *           + eps), every rounding fixed by the kernel's source (not by the compiler's contraction); then
+ *           ema = ema_decay * ema + (1 - ema_decay) * param where ema (n floats) is given.
  * max_norm <= 0 or +inf: clipping off (clip_state and ws are not touched and may be NULL); weight_decay == 0: no
- * decay; ema NULL: no average.  With all three off the result is srk_adam_step_state's (srk_adam_step_scaled's with a
- * scaler), bit for bit.  ws: srk_adamw_workspace_floats(n) floats, fully written before they are read.
+ * decay; ema NULL: no average.  srk_adam_step_state and srk_adam_step_scaled are this call with all three off
+ * (the same launches, the same bits).  ws: srk_adamw_workspace_floats(n) floats, fully written before they are read.
  * Checked on the host before any device work, SRK_ERR_INVALID with "adamw" and the argument's name in
  * srk_last_error(): n < 0; state NULL; param / grad / exp_avg / exp_avg_sq NULL with n > 0; param, grad, exp_avg,
  * exp_avg_sq, ema off 16 bytes, state off 8, scaler / clip_state / ws off 4; weight_decay negative or not finite;
@@ -763,8 +773,9 @@ int srk_specaug_draw(uint64_t* state, int64_t B, int64_t T, int64_t F, int W, in
  * are both NULL (label smoothing alone: lam_b = 1) or both given; with q_b = labels[partner_b] and eps = smoothing,
  *   t[b][c] = (1 - eps) (lam_b [c == y_b] + (1 - lam_b) [c == q_b]) + eps / C
  * (torch's label_smoothing on the mixed target), loss[0] = mean_b(logsumexp(z_b) - sum_c t[b][c] z[b][c]), dlogits
- * (nullable) = (softmax - t) / B.  ws: B + 1 floats; the same two launches and the same deterministic mean as
- * srk_cross_entropy, and with partner == lam == NULL and smoothing == 0 the same bits in loss and dlogits.  An
+ * (nullable) = (softmax - t) / B.  ws: B + 1 floats; one row kernel and one deterministic mean serve both entries
+ * (srk_cross_entropy passes no mix and no smoothing), so with partner == lam == NULL and smoothing == 0 loss and
+ * dlogits are srk_cross_entropy's bits.  An
  * out-of-range label (a row's own or its partner's), a partner outside [0, B) or a lam not in [0, 1] makes that
  * row's loss, and so the loss, NaN.  The host refuses, "cross_entropy" in srk_last_error(): smoothing outside
  * [0, 1) or not finite, a shape outside srk_cross_entropy's domain (or B >= 2^31), exactly one of partner / lam

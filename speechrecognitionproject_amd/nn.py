@@ -468,28 +468,8 @@ class Linear(tnn.Module):
 
 # ----------------------------------------------------------------------------- loss
 class _CrossEntropyFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, labels):
-        logits = logits.contiguous()
-        _check_cuda(logits)
-        B, C = logits.shape
-        labels = labels.to(device=logits.device, dtype=torch.int64).contiguous()
-        loss = torch.empty((), device=logits.device)
-        dlogits = torch.empty_like(logits) if ctx.needs_input_grad[0] else None
-        ws = torch.empty(B + 1, device=logits.device)
-        call("srk_cross_entropy", ptr(logits), ptr(labels), B, C, ptr(loss),
-             _optr(dlogits), ptr(ws), stream_ptr())
-        ctx.save_for_backward(dlogits)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        (dlogits,) = ctx.saved_tensors
-        return dlogits * g, None
-
-
-class _CrossEntropyMixFn(torch.autograd.Function):
-    """srk_cross_entropy_mix: the loss on the soft target of a mixed (partner, lam) and / or smoothed batch."""
+    """The loss on the hard target (srk_cross_entropy), or with a mix (partner, lam) and / or smoothing on the soft
+    target (srk_cross_entropy_mix): one kernel behind both, each entry with its own error texts."""
 
     @staticmethod
     def forward(ctx, logits, labels, partner, lam, smoothing):
@@ -506,8 +486,11 @@ class _CrossEntropyMixFn(torch.autograd.Function):
         loss = torch.empty((), device=logits.device)
         dlogits = torch.empty_like(logits) if ctx.needs_input_grad[0] else None
         ws = torch.empty(B + 1, device=logits.device)
-        call("srk_cross_entropy_mix", ptr(logits), ptr(labels), _optr(partner), _optr(lam), B, C, float(smoothing),
-             ptr(loss), _optr(dlogits), ptr(ws), stream_ptr())
+        if partner is None and lam is None and smoothing == 0.0:
+            call("srk_cross_entropy", ptr(logits), ptr(labels), B, C, ptr(loss), _optr(dlogits), ptr(ws), stream_ptr())
+        else:
+            call("srk_cross_entropy_mix", ptr(logits), ptr(labels), _optr(partner), _optr(lam), B, C, float(smoothing),
+                 ptr(loss), _optr(dlogits), ptr(ws), stream_ptr())
         ctx.save_for_backward(dlogits)
         return loss
 
@@ -532,10 +515,8 @@ class CrossEntropyLoss(tnn.Module):
 
     def forward(self, logits, labels, mix=None):
         require_gpu()
-        if mix is None and self.label_smoothing == 0.0:
-            return _CrossEntropyFn.apply(logits, labels)
         partner, lam = (None, None) if mix is None else mix
-        return _CrossEntropyMixFn.apply(logits, labels, partner, lam, self.label_smoothing)
+        return _CrossEntropyFn.apply(logits, labels, partner, lam, self.label_smoothing)
 
 
 # ----------------------------------------------------------------------------- 16-bit operand copies

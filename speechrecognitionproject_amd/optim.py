@@ -88,7 +88,7 @@ class FlatParams:
 
 class LossScaler:
     """Loss scaling for fp16 training, torch.cuda.amp.GradScaler semantics with its state on the
-    device (srk_grad_scaler_init / srk_adam_step_scaled), so a captured HIP graph replays it:
+    device (srk_grad_scaler_init, read by srk_adamw_step), so a captured HIP graph replays it:
 
         loss = criterion(model(x), y)
         scaler.scale(loss).backward()         # loss x scale (the scale is read on the device)
@@ -146,7 +146,8 @@ class Adam(torch.optim.Optimizer):
         read the result (synchronize);
       * ``ema_decay``: ``ema = d * ema + (1 - d) * p`` after every step that is not skipped, in a buffer that starts
         as a copy of the parameters; ``with optimizer.ema_weights(): ...`` evaluates or saves the averaged weights.
-    With all of them at their defaults, step() makes exactly the calls it made without them."""
+    With all of them at their defaults, step() launches the same kernels and produces the same bits as without them:
+    every configuration is one srk_adamw_step call, and what is off is a null pointer or a zero."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, flat=None, weight_decay=0.0,
                  decay_filter=_default_decay_filter, max_grad_norm=None, ema_decay=None):
@@ -181,7 +182,6 @@ class Adam(torch.optim.Optimizer):
             self._norm_ws = torch.empty(int(lib().srk_adamw_workspace_floats(self.flat.numel)), dtype=torch.float32,
                                         device=dev)
         self.ema = self.flat.data.clone() if self.ema_decay is not None else None
-        self._extended = bool(self.weight_decay) or self.max_grad_norm is not None or self.ema is not None
 
     @property
     def step_count(self):
@@ -246,20 +246,13 @@ class Adam(torch.optim.Optimizer):
         b1, b2 = g["betas"]
         f = self.flat
         self.sync_lr()
-        if self._extended:
-            call("srk_adamw_step", ptr(f.data), ptr(f.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), f.numel,
-                 float(b1), float(b2), float(g["eps"]), ptr(self.state_dev), float(self.grad_scale),
-                 _optr(scaler.state if scaler is not None else None), self.weight_decay, _optr(self.decay_mask),
-                 self.max_grad_norm if self.max_grad_norm is not None else 0.0, _optr(self.clip_state),
-                 _optr(self.ema), self.ema_decay if self.ema_decay is not None else 0.0, _optr(self._norm_ws),
-                 stream_ptr())
-        elif scaler is not None:
-            call("srk_adam_step_scaled", ptr(f.data), ptr(f.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), f.numel,
-                 float(b1), float(b2), float(g["eps"]), ptr(self.state_dev), float(self.grad_scale),
-                 ptr(scaler.state), stream_ptr())
-        else:
-            call("srk_adam_step_state", ptr(f.data), ptr(f.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), f.numel,
-                 float(b1), float(b2), float(g["eps"]), ptr(self.state_dev), float(self.grad_scale), stream_ptr())
+        # one entry for every configuration: what is off is a null pointer or a zero
+        call("srk_adamw_step", ptr(f.data), ptr(f.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), f.numel,
+             float(b1), float(b2), float(g["eps"]), ptr(self.state_dev), float(self.grad_scale),
+             _optr(scaler.state if scaler is not None else None), self.weight_decay, _optr(self.decay_mask),
+             self.max_grad_norm if self.max_grad_norm is not None else 0.0, _optr(self.clip_state),
+             _optr(self.ema), self.ema_decay if self.ema_decay is not None else 0.0, _optr(self._norm_ws),
+             stream_ptr())
         # a persistent kernel that timed out produced invalid gradients: fail loudly (a host-pinned
         # word, no device sync; it sees every timeout of the work the GPU has reached so far)
         check_health(sync=False)

@@ -5,10 +5,14 @@
 One process, alternating rounds:
 
 (a) at the flat parameter counts of mfcc_bgru and fbanks_cnn: the gradient-norm pass (srk_adamw_step's first launch,
-    4 B n read) next to a device copy (torch ``copy_``, 8 B n) of the same buffer, and the extended update with decay,
-    clip and EMA all on (28 B n + 8 B n + n / 64 B) next to adam_state_kernel (28 B n) on the same buffers.  The
-    kernels alone come from the library's event pair around each launch (srk_prof categories "grad_norm", "adamw",
-    "adam"); the whole calls (prep launch and host cost included) from device events around --iters calls;
+    4 B n read) next to a device copy (torch ``copy_``, 8 B n) of the same buffer, and the update loop with decay, clip
+    and EMA all on (adam_state_kernel, 28 B n + 8 B n + n / 64 B, key "adamw_kernel") next to the same loop with
+    everything off (adam_plain_kernel, 28 B n; the key is still "adam_state_kernel") on the same buffers.  The
+    kernels alone come from the library's event pair around each launch (srk_prof categories "grad_norm", "adamw", "adam"), one mean per
+    round; the whole calls (prep launch and host cost included) from device events around --iters calls.  The finite
+    check of a loss-scaled step (grad_norm_kernel<false>, category "grad_check", 4 B n) is timed the same way through
+    srk_adam_step_scaled ("grad_check_kernel") and through srk_adamw_step with a scaler alone
+    ("grad_check_adamw_kernel");
 (b) the mfcc_bgru (cfg2: batch 256, fp32) and fbanks_cnn train steps (forward, loss, backward, optimizer) replayed
     from a HIP graph, without the flags and with ``--clip-grad-norm 1 --weight-decay 0.01 --ema 0.999`` in the same
     rounds: ms per step, utt/s and the ratio, beside the spread of the same run, and next to it what the extra bytes
@@ -96,16 +100,45 @@ def bench_kernels(n, rounds, iters):
             e["gb_per_s"] = round(nbytes / (e["us"] * 1e-6) / 1e9, 1)
         res[k] = e
     # the kernels alone, by the library's own event pair around each launch
-    _lib.prof_enable(True)
-    for _ in range(iters):
-        old()
-        new()
-    torch.cuda.synchronize()
-    for name, key in (("grad_norm", "norm_kernel"), ("adamw", "adamw_kernel"), ("adam", "adam_state_kernel")):
-        launches, ms, nbytes = _lib.prof_read(name)
-        res[key] = {"launches": launches, "us": round(ms / launches * 1e3, 2), "bytes": nbytes / launches,
-                    "gb_per_s": round(nbytes / (ms * 1e-3) / 1e9, 1)}
-    _lib.prof_enable(False)
+    cats = (("grad_norm", "norm_kernel"), ("adamw", "adamw_kernel"), ("adam", "adam_state_kernel"))
+    per_round, per_launch_bytes = {key: [] for _, key in cats}, {}
+    for _ in range(rounds):
+        _lib.prof_enable(True)
+        for _ in range(iters):
+            old()
+            new()
+        torch.cuda.synchronize()
+        for name, key in cats:
+            launches, ms, nbytes = _lib.prof_read(name)
+            per_round[key].append(ms / launches)
+            per_launch_bytes[key] = nbytes / launches
+        _lib.prof_enable(False)
+    for _, key in cats:
+        e = summarize(per_round[key])
+        e.update(launches=rounds * iters, bytes=per_launch_bytes[key],
+                 gb_per_s=round(per_launch_bytes[key] / (e["us"] * 1e-6) / 1e9, 1))
+        res[key] = e
+    # the finite check of a scaled step (static scale, finite gradients: every step updates), through both entries
+    sc = torch.zeros(8, dtype=torch.int32, device="cuda")
+    _lib.call("srk_grad_scaler_init", ptr(sc), 1.0, 2.0, 0.5, 0, stream_ptr())
+    checks = {"grad_check_kernel": lambda: _lib.call(
+                  "srk_adam_step_scaled", ptr(p), ptr(grad), ptr(m), ptr(v), n, B1, B2, EPS, ptr(st), 1.0, ptr(sc),
+                  stream_ptr()),
+              "grad_check_adamw_kernel": lambda: _lib.call(
+                  "srk_adamw_step", ptr(p), ptr(grad), ptr(m), ptr(v), n, B1, B2, EPS, ptr(st), 1.0, ptr(sc), 0.0, None,
+                  0.0, None, None, 0.0, None, stream_ptr())}
+    per_round = {k: [] for k in checks}
+    for _ in range(rounds):
+        for key, call in checks.items():
+            _lib.prof_enable(True)
+            for _ in range(iters):
+                call()
+            torch.cuda.synchronize()
+            launches, ms, nbytes = _lib.prof_read("grad_check")
+            _lib.prof_enable(False)
+            per_round[key].append(ms / launches)
+    for key, samples in per_round.items():
+        res[key] = dict(summarize(samples), bytes=4.0 * n)
     res["norm_over_copy"] = round(res["norm_kernel"]["us"] / res["copy"]["us"], 3)
     res["adamw_over_adam_kernel"] = round(res["adamw_kernel"]["us"] / res["adam_state_kernel"]["us"], 3)
     res["adamw_over_adam_bytes"] = round(res["adamw_kernel"]["bytes"] / res["adam_state_kernel"]["bytes"], 3)

@@ -38,7 +38,8 @@ GROUPS = {  # srk_prof name -> substrings of the rocprof kernel symbols it cover
     "gru_fwd_step": ("gru_fwd_step_kernel",), "gru_bwd_step": ("gru_bwd_step_kernel",),
     "mfcc": ("mfcc3_kernel", "mfcc2_kernel"), "fbank": ("fbank_kernel",), "spec": ("spec_kernel",),
     "conv_fwd": (), "conv_dgrad": (), "conv_wgrad": (), "conv_fwd_lp": (), "conv_dgrad_lp": (), "conv_wgrad_lp": (),
-    "adam": ("adam_kernel",), "noise_mix": ("noise_mix_kernel",),
+    # adam_plain_kernel also runs a scaler-only step, which srk_prof books as "adamw" (no group here)
+    "adam": ("adam_plain_kernel", "adam_host_kernel"), "noise_mix": ("noise_mix_kernel",),
 }
 
 
