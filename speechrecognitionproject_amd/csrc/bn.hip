@@ -132,33 +132,40 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
   }
 }
 
-// The reduction kernels below load the partials of kPre chunks before any is combined (an in-order sum
-// that no longer waits out one load latency per chunk).
+// The combines below walk the chunk partials of channel c (chunks first .. chunks - 1 of the arrays
+// pa, pb [chunks][C]) with this loop: the partials of kPre chunks are loaded before any is consumed (an in-order
+// pass that no longer waits out one load latency per chunk; the tail's addresses are clamped), then
+// step(is the last chunk, pa[k], pb[k]) runs in chunk order.
 constexpr int kPre = 32;
+template <class Step>
+__device__ __forceinline__ void for_chunk_partials(const float* __restrict__ pa, const float* __restrict__ pb,
+                                                   int first, int chunks, int C, int c, Step step) {
+  for (int k0 = first; k0 < chunks; k0 += kPre) {
+    float va[kPre], vb[kPre];
+#pragma unroll
+    for (int u = 0; u < kPre; ++u) {
+      const int64_t k = k0 + u < chunks ? k0 + u : chunks - 1;
+      va[u] = pa[k * C + c];
+      vb[u] = pb[k * C + c];
+    }
+#pragma unroll
+    for (int u = 0; u < kPre; ++u) {
+      if (k0 + u < chunks) step(k0 + u == chunks - 1, va[u], vb[u]);
+    }
+  }
+}
 
-// Combine the chunk partials of channel c in chunk order (Chan), one lane (srk option bn_tree = 0).
+// Combine the chunk partials of channel c in chunk order (Chan), one lane (srk option bn_tree = 2).  Every chunk
+// but the last has rows_per_chunk rows.
 __device__ __forceinline__ void combine_chunks(const float* __restrict__ pmean, const float* __restrict__ pm2,
                                                const BnGeom& g, int c, float& n, float& mu, float& m2) {
+  const float rpc = (float)g.rows_per_chunk;
+  const float last = (float)(g.M - (int64_t)(g.chunks - 1) * g.rows_per_chunk);
   n = 0.f;
   mu = 0.f;
   m2 = 0.f;
-  for (int k0 = 0; k0 < g.chunks; k0 += kPre) {
-    float vm[kPre], v2[kPre];
-#pragma unroll
-    for (int u = 0; u < kPre; ++u) {
-      const int64_t k = k0 + u < g.chunks ? k0 + u : g.chunks - 1;
-      vm[u] = pmean[k * g.C + c];
-      v2[u] = pm2[k * g.C + c];
-    }
-#pragma unroll
-    for (int u = 0; u < kPre; ++u) {
-      if (k0 + u < g.chunks) {
-        const int64_t r0 = (int64_t)(k0 + u) * g.rows_per_chunk;
-        const float nb = (float)((r0 + g.rows_per_chunk < g.M ? g.rows_per_chunk : g.M - r0));
-        chan(n, mu, m2, nb, vm[u], v2[u]);
-      }
-    }
-  }
+  for_chunk_partials(pmean, pm2, 0, g.chunks, g.C, c,
+                     [&](bool is_last, float vm, float v2) { chan(n, mu, m2, is_last ? last : rpc, vm, v2); });
 }
 
 // combine_chunks's arithmetic, bit for bit, without its dependent divides: every chunk has >= 1 row, so
@@ -173,24 +180,12 @@ __device__ __forceinline__ void combine_chunks_fast(const float* __restrict__ pm
   n = g.chunks == 1 ? last : rpc;
   mu = pmean[c];
   m2 = pm2[c];
-  for (int k0 = 1; k0 < g.chunks; k0 += kPre) {
-    float vm[kPre], v2[kPre];
-#pragma unroll
-    for (int u = 0; u < kPre; ++u) {
-      const int64_t k = k0 + u < g.chunks ? k0 + u : g.chunks - 1;
-      vm[u] = pmean[k * g.C + c];
-      v2[u] = pm2[k * g.C + c];
-    }
-#pragma unroll
-    for (int u = 0; u < kPre; ++u) {
-      if (k0 + u < g.chunks) {
-        const float nb = k0 + u == g.chunks - 1 ? last : rpc;
-        const float nt = n + nb;
-        chan_step(n, mu, m2, nb, nt, vm[u], v2[u]);
-        n = nt;
-      }
-    }
-  }
+  for_chunk_partials(pmean, pm2, 1, g.chunks, g.C, c, [&](bool is_last, float vm, float v2) {
+    const float nb = is_last ? last : rpc;
+    const float nt = n + nb;
+    chan_step(n, mu, m2, nb, nt, vm, v2);
+    n = nt;
+  });
 }
 
 // Combine the chunk partials of channel c (Chan's pairwise formula) as a fixed pairwise tree, one wave
@@ -363,7 +358,8 @@ __global__ void bn_dgamma_kernel(const float* __restrict__ p0, const float* __re
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   float a = 0.f, b = 0.f;
-  for (int k0 = 0; k0 < chunks; k0 += kPre) {   // loads ahead of the in-order sums (see combine_chunks)
+  // for_chunk_partials's loop, written out: through the template the adds come out with their operands commuted
+  for (int k0 = 0; k0 < chunks; k0 += kPre) {
     float v0[kPre], v1[kPre];
 #pragma unroll
     for (int u = 0; u < kPre; ++u) {
@@ -463,39 +459,58 @@ __global__ void bn_combine_kernel(const float* __restrict__ all, int world, int 
 
 ScratchPool g_bs;   // per-chunk statistics / reduction partials
 
-// the element kernels by index width (32-bit channel arithmetic below 2^32 elements) and 16-bit copy
-template <int LP>
-void launch_apply_lp(int64_t M, int C, hipStream_t s, const float* x, const float* mean, const float* invstd,
-                     const float* gamma, const float* beta, const float* residual, int relu, float* y, uint16_t* y16,
-                     uint8_t* mask) {
+// One call's reduction over (M, C): the geometry, the grid of the two chunk kernels and their partial arrays
+// [chunks][C] (a producer that formed the chunk partials itself would write p0 / p1 in launch_stats's place)
+struct BnPlan {
+  BnGeom g;
+  dim3 grid;
+  float *p0, *p1;
+};
+int bn_plan(int64_t M, int64_t C, BnPlan* p) {
+  const BnGeom g = p->g = bn_geom(M, (int)C);
+  p->grid = dim3((unsigned)((g.C4 + g.CQ - 1) / g.CQ), (unsigned)g.chunks);
+  if (int rc = g_bs.get((size_t)2 * g.chunks * C, &p->p0)) return rc;
+  p->p1 = p->p0 + (size_t)g.chunks * C;
+  return SRK_OK;
+}
+
+void launch_stats(const BnPlan& p, const float* x, hipStream_t s) {
+  hipLaunchKernelGGL(bn_stats_kernel, p.grid, dim3(256), 0, s, x, p.g, p.p0, p.p1);
+}
+
+// form = option bn_tree (0 for any value outside its range): one lane per channel in 64-lane blocks (in order:
+// C / 64 waves over the chip) or one wave per channel, four to a block (tree)
+void launch_finalize(const BnPlan& p, int form, float eps, float momentum, float* mean, float* invstd,
+                     float* running_mean, float* running_var, hipStream_t s) {
+  static const struct {
+    decltype(&bn_finalize_kernel<0>) kernel;
+    int channels, threads;   // per block
+  } forms[3] = {{bn_finalize_kernel<0>, 64, 64}, {bn_finalize_kernel<1>, 4, 256}, {bn_finalize_kernel<2>, 64, 64}};
+  const auto& f = forms[form == 1 || form == 2 ? form : 0];
+  hipLaunchKernelGGL(f.kernel, dim3((unsigned)((p.g.C + f.channels - 1) / f.channels)), dim3(f.threads), 0, s, p.p0,
+                     p.p1, p.g, eps, momentum, mean, invstd, running_mean, running_var);
+}
+
+// out0 = sum g, out1 = sum g * xhat per channel, also added into acc0 / acc1 where given
+void launch_bwd_sums(const BnPlan& p, const float* x, const float* y, const uint8_t* mask, const float* dy,
+                     const float* mean, const float* invstd, int relu, float* out0, float* out1, float* acc0,
+                     float* acc1, hipStream_t s) {
+  hipLaunchKernelGGL(bn_bwd_partial_kernel, p.grid, dim3(256), 0, s, x, y, mask, dy, p.g, mean, invstd, relu, p.p0,
+                     p.p1);
+  hipLaunchKernelGGL(bn_dgamma_kernel, dim3((unsigned)((p.g.C + 255) / 256)), dim3(256), 0, s, p.p0, p.p1, p.g.chunks,
+                     p.g.C, out0, out1, acc0, acc1);
+}
+
+// The element kernels' instantiations as [32-bit channel arithmetic][16-bit copy: 0 none, 1 bf16, 2 fp16]
+#define SRK_BN_ELEMENT_KERNELS(K) {{K<false, 0>, K<false, 1>, K<false, 2>}, {K<true, 0>, K<true, 1>, K<true, 2>}}
+const decltype(&bn_apply_kernel<true, 0>) kApplyKernels[2][3] = SRK_BN_ELEMENT_KERNELS(bn_apply_kernel);
+const decltype(&bn_dx_kernel<true, 0>) kDxKernels[2][3] = SRK_BN_ELEMENT_KERNELS(bn_dx_kernel);
+
+// The element pass over (M, C), one lane per quad, 32-bit channel arithmetic below 2^32 elements; args: the kernel's
+template <class K, class... Args>
+void launch_elements(K* const (&kernels)[2][3], int lp, int64_t M, int C, hipStream_t s, Args... args) {
   const int64_t n4 = M * C / 4;
-  hipLaunchKernelGGL((M * C < (1LL << 32) ? bn_apply_kernel<true, LP> : bn_apply_kernel<false, LP>),
-                     dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, x, M, C, mean, invstd, gamma, beta, residual,
-                     relu, y, y16, mask);
-}
-void launch_apply(int LP, int64_t M, int C, hipStream_t s, const float* x, const float* mean, const float* invstd,
-                  const float* gamma, const float* beta, const float* residual, int relu, float* y, uint16_t* y16,
-                  uint8_t* mask = nullptr) {
-  if (LP == 1) launch_apply_lp<1>(M, C, s, x, mean, invstd, gamma, beta, residual, relu, y, y16, mask);
-  else if (LP == 2) launch_apply_lp<2>(M, C, s, x, mean, invstd, gamma, beta, residual, relu, y, y16, mask);
-  else launch_apply_lp<0>(M, C, s, x, mean, invstd, gamma, beta, residual, relu, y, nullptr, mask);
-}
-template <int LP>
-void launch_dx_lp(int64_t M, int C, hipStream_t s, const float* x, const float* y, const uint8_t* mask, const float* dy,
-                  const float* mean, const float* invstd, const float* gamma, const float* dbeta, const float* dgamma,
-                  int relu, int train, float m_norm, const float* m_norm_dev, float* dx, float* dres, uint16_t* dx16) {
-  const int64_t n4 = M * C / 4;
-  hipLaunchKernelGGL((M * C < (1LL << 32) ? bn_dx_kernel<true, LP> : bn_dx_kernel<false, LP>),
-                     dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, x, y, mask, dy, M, C, mean, invstd, gamma,
-                     dbeta, dgamma, relu, train, m_norm, m_norm_dev, dx, dres, dx16);
-}
-void launch_dx(int LP, int64_t M, int C, hipStream_t s, const float* x, const float* y, const uint8_t* mask,
-               const float* dy, const float* mean, const float* invstd, const float* gamma, const float* dbeta,
-               const float* dgamma, int relu, int train, float m_norm, const float* m_norm_dev, float* dx, float* dres,
-               uint16_t* dx16) {
-  if (LP == 1) launch_dx_lp<1>(M, C, s, x, y, mask, dy, mean, invstd, gamma, dbeta, dgamma, relu, train, m_norm, m_norm_dev, dx, dres, dx16);
-  else if (LP == 2) launch_dx_lp<2>(M, C, s, x, y, mask, dy, mean, invstd, gamma, dbeta, dgamma, relu, train, m_norm, m_norm_dev, dx, dres, dx16);
-  else launch_dx_lp<0>(M, C, s, x, y, mask, dy, mean, invstd, gamma, dbeta, dgamma, relu, train, m_norm, m_norm_dev, dx, dres, nullptr);
+  hipLaunchKernelGGL(kernels[M * C < (1LL << 32)][lp], dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, args...);
 }
 
 // 16-bit copy requested and possible: the matmul precision's type (1 bf16, 2 fp16), else 0
@@ -540,31 +555,17 @@ int srk_batchnorm_fwd16_mask(const float* x, int64_t M, int64_t C, const float* 
   const bool mk = relu && relu_mask;
   srk::ProfScope prof("batchnorm_fwd", s,
                       ((training ? 12.0 : 8.0) + (lp ? 2.0 : 0.0) + (mk ? 0.25 : 0.0)) * (double)M * C);
-  const srk::BnGeom g = srk::bn_geom(M, (int)C);
   if (training) {
-    float* part = nullptr;
-    if (int rc = srk::g_bs.get((size_t)2 * g.chunks * C, &part)) return rc;
-    hipLaunchKernelGGL(srk::bn_stats_kernel, dim3((unsigned)((g.C4 + g.CQ - 1) / g.CQ), (unsigned)g.chunks), dim3(256),
-                       0, s, x, g, part, part + (size_t)g.chunks * C);
-    // one wave per channel (tree) or one lane per channel in 64-lane blocks (in order: C / 64 waves over the chip)
-    if (srk::g_opt_bn_tree == 1)
-      hipLaunchKernelGGL(srk::bn_finalize_kernel<1>, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, s, part,
-                         part + (size_t)g.chunks * C, g, eps, momentum, save_mean, save_invstd, running_mean,
-                         running_var);
-    else if (srk::g_opt_bn_tree == 2)
-      hipLaunchKernelGGL(srk::bn_finalize_kernel<2>, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, s, part,
-                         part + (size_t)g.chunks * C, g, eps, momentum, save_mean, save_invstd, running_mean,
-                         running_var);
-    else
-      hipLaunchKernelGGL(srk::bn_finalize_kernel<0>, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, s, part,
-                         part + (size_t)g.chunks * C, g, eps, momentum, save_mean, save_invstd, running_mean,
-                         running_var);
+    srk::BnPlan plan;
+    if (int rc = srk::bn_plan(M, C, &plan)) return rc;
+    srk::launch_stats(plan, x, s);
+    srk::launch_finalize(plan, srk::g_opt_bn_tree, eps, momentum, save_mean, save_invstd, running_mean, running_var, s);
   } else {
     hipLaunchKernelGGL(srk::bn_eval_stats_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, running_mean,
                        running_var, (int)C, eps, save_mean, save_invstd);
   }
-  srk::launch_apply(lp, M, (int)C, s, x, save_mean, save_invstd, gamma, beta, residual, relu, y,
-                    static_cast<uint16_t*>(y16), mk ? relu_mask : nullptr);
+  srk::launch_elements(srk::kApplyKernels, lp, M, (int)C, s, x, M, (int)C, save_mean, save_invstd, gamma, beta, residual,
+                       relu, y, static_cast<uint16_t*>(y16), mk ? relu_mask : nullptr);
   SRK_CHECK_HIP(hipGetLastError());
   if (lp && y16_written) *y16_written = 1;
   return SRK_OK;
@@ -607,15 +608,11 @@ int srk_batchnorm_bwd16_mask(const float* x, const float* y, const uint8_t* relu
   const uint8_t* mk = relu ? relu_mask : nullptr;
   // algorithmic bytes: x, dy and y (or its mask bits) read twice, dx written (+ its 16-bit copy)
   srk::ProfScope prof("batchnorm_bwd", s, ((mk ? 12.5 : 16.0) + (lp ? 2.0 : 0.0)) * (double)M * C);
-  const srk::BnGeom g = srk::bn_geom(M, (int)C);
-  float* part = nullptr;
-  if (int rc = srk::g_bs.get((size_t)2 * g.chunks * C, &part)) return rc;
-  hipLaunchKernelGGL(srk::bn_bwd_partial_kernel, dim3((unsigned)((g.C4 + g.CQ - 1) / g.CQ), (unsigned)g.chunks),
-                     dim3(256), 0, s, x, y, mk, dy, g, save_mean, save_invstd, relu, part, part + (size_t)g.chunks * C);
-  hipLaunchKernelGGL(srk::bn_dgamma_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, part,
-                     part + (size_t)g.chunks * C, g.chunks, (int)C, dbeta, dgamma, dbeta_acc, dgamma_acc);
-  srk::launch_dx(lp, M, (int)C, s, x, y, mk, dy, save_mean, save_invstd, gamma, dbeta, dgamma, relu, training,
-                 (float)M, nullptr, dx, dresidual, static_cast<uint16_t*>(dx16));
+  srk::BnPlan plan;
+  if (int rc = srk::bn_plan(M, C, &plan)) return rc;
+  srk::launch_bwd_sums(plan, x, y, mk, dy, save_mean, save_invstd, relu, dbeta, dgamma, dbeta_acc, dgamma_acc, s);
+  srk::launch_elements(srk::kDxKernels, lp, M, (int)C, s, x, y, mk, dy, M, (int)C, save_mean, save_invstd, gamma, dbeta,
+                       dgamma, relu, training, (float)M, nullptr, dx, dresidual, static_cast<uint16_t*>(dx16));
   SRK_CHECK_HIP(hipGetLastError());
   if (lp && dx16_written) *dx16_written = 1;
   return SRK_OK;
@@ -630,13 +627,11 @@ int srk_batchnorm_stats(const float* x, int64_t M, int64_t C, float* stats, void
   SRK_REQUIRE(x && stats, SRK_ERR_INVALID, "batchnorm_stats: null pointer");
   hipStream_t s = srk::as_stream(stream);
   srk::ProfScope prof("batchnorm_fwd", s, 4.0 * (double)M * C);
-  const srk::BnGeom g = srk::bn_geom(M, (int)C);
-  float* part = nullptr;
-  if (int rc = srk::g_bs.get((size_t)2 * g.chunks * C, &part)) return rc;
-  hipLaunchKernelGGL(srk::bn_stats_kernel, dim3((unsigned)((g.C4 + g.CQ - 1) / g.CQ), (unsigned)g.chunks), dim3(256), 0,
-                     s, x, g, part, part + (size_t)g.chunks * C);
-  hipLaunchKernelGGL(srk::bn_local_stats_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, s, part,
-                     part + (size_t)g.chunks * C, g, stats);
+  srk::BnPlan plan;
+  if (int rc = srk::bn_plan(M, C, &plan)) return rc;
+  srk::launch_stats(plan, x, s);
+  hipLaunchKernelGGL(srk::bn_local_stats_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, s, plan.p0, plan.p1,
+                     plan.g, stats);
   SRK_CHECK_HIP(hipGetLastError());
   return SRK_OK;
   SRK_API_END
@@ -665,7 +660,8 @@ int srk_batchnorm_apply(const float* x, int64_t M, int64_t C, const float* save_
   SRK_REQUIRE(x && save_mean && save_invstd && gamma && beta && y, SRK_ERR_INVALID, "batchnorm_apply: null pointer");
   hipStream_t s = srk::as_stream(stream);
   srk::ProfScope prof("batchnorm_fwd", s, 8.0 * (double)M * C);
-  srk::launch_apply(0, M, (int)C, s, x, save_mean, save_invstd, gamma, beta, residual, relu, y, nullptr);
+  srk::launch_elements(srk::kApplyKernels, 0, M, (int)C, s, x, M, (int)C, save_mean, save_invstd, gamma, beta, residual,
+                       relu, y, nullptr, nullptr);
   SRK_CHECK_HIP(hipGetLastError());
   return SRK_OK;
   SRK_API_END
@@ -678,14 +674,9 @@ int srk_batchnorm_bwd_reduce(const float* x, const float* y, const float* dy, in
   SRK_REQUIRE(x && y && dy && save_mean && save_invstd && sums, SRK_ERR_INVALID, "batchnorm_bwd_reduce: null pointer");
   hipStream_t s = srk::as_stream(stream);
   srk::ProfScope prof("batchnorm_bwd", s, 12.0 * (double)M * C);
-  const srk::BnGeom g = srk::bn_geom(M, (int)C);
-  float* part = nullptr;
-  if (int rc = srk::g_bs.get((size_t)2 * g.chunks * C, &part)) return rc;
-  hipLaunchKernelGGL(srk::bn_bwd_partial_kernel, dim3((unsigned)((g.C4 + g.CQ - 1) / g.CQ), (unsigned)g.chunks),
-                     dim3(256), 0, s, x, y, nullptr, dy, g, save_mean, save_invstd, relu, part,
-                     part + (size_t)g.chunks * C);
-  hipLaunchKernelGGL(srk::bn_dgamma_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, part,
-                     part + (size_t)g.chunks * C, g.chunks, (int)C, sums, sums + C, nullptr, nullptr);
+  srk::BnPlan plan;
+  if (int rc = srk::bn_plan(M, C, &plan)) return rc;
+  srk::launch_bwd_sums(plan, x, y, nullptr, dy, save_mean, save_invstd, relu, sums, sums + C, nullptr, nullptr, s);
   SRK_CHECK_HIP(hipGetLastError());
   return SRK_OK;
   SRK_API_END
@@ -701,8 +692,8 @@ int srk_batchnorm_bwd_dx(const float* x, const float* y, const float* dy, int64_
               SRK_ERR_INVALID, "batchnorm_bwd_dx: null pointer");
   hipStream_t s = srk::as_stream(stream);
   srk::ProfScope prof("batchnorm_bwd", s, 16.0 * (double)M * C);
-  srk::launch_dx(0, M, (int)C, s, x, y, nullptr, dy, save_mean, save_invstd, gamma, sums, sums + C, relu, 1, 0.f,
-                 total_count, dx, dresidual, nullptr);
+  srk::launch_elements(srk::kDxKernels, 0, M, (int)C, s, x, y, nullptr, dy, M, (int)C, save_mean, save_invstd, gamma,
+                       sums, sums + C, relu, 1, 0.f, total_count, dx, dresidual, nullptr);
   SRK_CHECK_HIP(hipGetLastError());
   return SRK_OK;
   SRK_API_END

@@ -587,22 +587,30 @@ def _x16_handover(x, Ci, Co, pop, w_needs_grad):
     return x16, written
 
 
-def _dw_target(ctx, w):
-    """(dw, accumulate) of a conv backward: the FlatParams-owned .grad of ctx.w_param, which the kernel that forms
-    the weight gradient ADDS it into (no autograd add kernel), else a fresh tensor returned to autograd."""
-    gw = _flat_grad(ctx.w_param) if ctx.needs_input_grad[1] and INPLACE_GRADS else None
-    return (gw, 1) if gw is not None else (torch.empty_like(w), 0)
+def _param_grad_target(ctx, params):
+    """Where a backward may ADD the gradients of `params` (a conv's weight; BatchNorm's gamma and beta), the
+    Function's inputs 1, 2, ..: their FlatParams-owned .grad buffers when every one of them has one (all or none;
+    the kernel that forms the gradients then adds them in, no autograd add kernel), else None: the gradients go
+    into fresh tensors and back to autograd."""
+    flat = [_flat_grad(p) if ctx.needs_input_grad[1 + i] and INPLACE_GRADS else None for i, p in enumerate(params)]
+    return flat if all(g is not None for g in flat) else None
 
 
-def _dw_done(ctx, dw, accumulate):
-    """What the backward returns for the weight after the call: None once accumulated in place (the gradient
-    reducer is told), else dw in the parameter's shape."""
-    if not accumulate:
-        return dw.view(ctx.w_param.shape)
-    red = _reducer_of(ctx.w_param)
+def _param_grad_done(params, grads, accumulated):
+    """What the backward returns for `params` after the call: None for each once accumulated in place (the gradient
+    reducer is told once, with all of them), else the gradients in the parameters' shapes."""
+    if not accumulated:
+        return [g.view(p.shape) for g, p in zip(grads, params)]
+    red = _reducer_of(params[0])
     if red is not None:
-        red.mark_ready([ctx.w_param])
-    return None
+        red.mark_ready(list(params))
+    return [None] * len(params)
+
+
+def _dw_target(ctx, w):
+    """(dw, accumulate) of a conv backward: ctx.w_param's own .grad to add into, else a fresh tensor like w."""
+    flat = _param_grad_target(ctx, [ctx.w_param])
+    return (flat[0], 1) if flat else (torch.empty_like(w), 0)
 
 
 def _conv_operands(x, w, b):
@@ -666,7 +674,7 @@ class _Conv2dNHWCFn(torch.autograd.Function):
         dy, dy16, dx, dw, acc, db, ws, x16 = _conv_backward_buffers(ctx, dy, x, w, has_b, KH, KW)
         call("srk_conv2d_nhwc_bwd16_acc", ptr(x), N, H, W, Ci, ptr(w), Co, KH, KW, ph, pw, sh, sw, ptr(dy),
              _optr(dy16), _optr(dx), ptr(dw), _optr(db), ptr(ws), _optr(x16), acc, stream_ptr())
-        return dx, _dw_done(ctx, dw, acc), db, None, None
+        return dx, *_param_grad_done([ctx.w_param], [dw], acc), db, None, None
 
 
 class Conv2d(tnn.Module):
@@ -712,7 +720,7 @@ class _Conv1dDilFn(torch.autograd.Function):
         dy, dy16, dx, dw, acc, db, ws, x16 = _conv_backward_buffers(ctx, dy, x, w, has_b, 1, K)
         call("srk_conv1d_nlc_dil_bwd", ptr(x), N, L, Ci, ptr(w), Co, K, pad, dil, ptr(dy), _optr(dy16), _optr(dx),
              ptr(dw), _optr(db), ptr(ws), _optr(x16), acc, stream_ptr())
-        return dx, _dw_done(ctx, dw, acc), db, None, None
+        return dx, *_param_grad_done([ctx.w_param], [dw], acc), db, None, None
 
 
 class Conv1d(tnn.Module):
@@ -957,7 +965,7 @@ class _DepthwiseConv2dFn(torch.autograd.Function):
                          device=x.device)
         call("srk_dwconv2d_nhwc_bwd", ptr(x), N, H, W, C, ptr(w), KH, KW, ph, pw, sh, sw, ptr(dy), _optr(dx), ptr(dw),
              _optr(db), ptr(ws), acc, stream_ptr())
-        return dx, _dw_done(ctx, dw, acc), db, None, None
+        return dx, *_param_grad_done([ctx.w_param], [dw], acc), db, None, None
 
 
 class DepthwiseConv2d(tnn.Module):
@@ -1130,14 +1138,7 @@ class Dropout(tnn.Module):
 class _BatchNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, residual, running_mean, running_var, training, momentum, eps, relu):
-        x = x.contiguous()
-        C = x.shape[-1]
-        M = x.numel() // C
-        _check_cuda(x, gamma, beta, residual)
-        y = torch.empty_like(x)
-        mean = torch.empty(C, device=x.device)
-        invstd = torch.empty(C, device=x.device)
-        res = residual.contiguous() if residual is not None else None
+        x, M, C, y, mean, invstd, res = _bn_operands(x, gamma, beta, residual)
         y16, written = None, ctypes.c_int(0)
         if training and any(ctx.needs_input_grad[:4]) and _copy16_wanted(C):   # the consuming conv's 16-bit copy of y
             y16 = torch.empty(y.numel(), device=x.device, dtype=torch.int16)
@@ -1160,34 +1161,41 @@ class _BatchNormFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, y, gamma, mean, invstd = ctx.saved_tensors
         training, relu, has_res = ctx.flags
-        C = x.shape[-1]
-        M = x.numel() // C
-        dy = dy.contiguous()
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        dres = torch.empty_like(x) if has_res and ctx.needs_input_grad[3] else None
-        dgamma = torch.empty(C, device=x.device)
-        dbeta = torch.empty(C, device=x.device)
+        dy, M, C, dx, dres = _bn_backward_buffers(ctx, dy, x, has_res)
         _copy16_drop(y)   # the forward's copy: its consumers' backward has run
         dx16, written = None, ctypes.c_int(0)
         if dx is not None and _copy16_wanted(C):   # dx is the producing conv's dY
             dx16 = torch.empty(dx.numel(), device=x.device, dtype=torch.int16)
-        # dgamma / dbeta also ADDED to FlatParams-owned .grad buffers in the kernel that forms them
-        gp, bp = ctx.params
-        gg = _flat_grad(gp) if ctx.needs_input_grad[1] and INPLACE_GRADS else None
-        gb = _flat_grad(bp) if ctx.needs_input_grad[2] and INPLACE_GRADS else None
-        acc = gg is not None and gb is not None
+        # dgamma / dbeta are also ADDED to FlatParams-owned .grad buffers in the kernel that forms them
+        acc = _param_grad_target(ctx, ctx.params)
+        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
         mask, ctx.mask = ctx.mask, None
         call("srk_batchnorm_bwd16_mask", ptr(x), ptr(y), _optr(mask), ptr(dy), M, C,
              ptr(gamma), ptr(mean), ptr(invstd), training, relu, _optr(dx), _optr(dx16), ctypes.byref(written),
-             ptr(dgamma), ptr(dbeta), _optr(dres), ptr(gg) if acc else None, ptr(gb) if acc else None, stream_ptr())
+             ptr(dgamma), ptr(dbeta), _optr(dres), ptr(acc[0]) if acc else None, ptr(acc[1]) if acc else None,
+             stream_ptr())
         if written.value:
             _copy16_put(dx, dx16)
-        if acc:
-            red = _reducer_of(gp)
-            if red is not None:
-                red.mark_ready([gp, bp])
-            return dx, None, None, dres, None, None, None, None, None, None
-        return dx, dgamma, dbeta, dres, None, None, None, None, None, None
+        return (dx, *_param_grad_done(ctx.params, (dgamma, dbeta), acc), dres) + (None,) * 6
+
+
+# What _BatchNormFn and _SyncBatchNormFn share around their library calls.
+def _bn_operands(x, gamma, beta, residual):
+    """(x, M, C, y, mean, invstd, residual) of a forward: x and the residual contiguous, the operands checked, y and
+    the saved statistics allocated."""
+    x = x.contiguous()
+    C = x.shape[-1]
+    _check_cuda(x, gamma, beta, residual)
+    mean, invstd = torch.empty(C, device=x.device), torch.empty(C, device=x.device)
+    return x, x.numel() // C, C, torch.empty_like(x), mean, invstd, None if residual is None else residual.contiguous()
+
+
+def _bn_backward_buffers(ctx, dy, x, has_res):
+    """(contiguous dy, M, C, dx or None, dresidual or None) of a backward."""
+    C = x.shape[-1]
+    dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+    dres = torch.empty_like(x) if has_res and ctx.needs_input_grad[3] else None
+    return dy.contiguous(), x.numel() // C, C, dx, dres
 
 
 class BatchNorm1d(tnn.Module):
@@ -1256,10 +1264,7 @@ class _SyncBatchNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, residual, running_mean, running_var, momentum, eps, relu, group):
         import torch.distributed as dist
-        x = x.contiguous()
-        C = x.shape[-1]
-        M = x.numel() // C
-        _check_cuda(x, gamma, beta, residual)
+        x, M, C, y, mean, invstd, res = _bn_operands(x, gamma, beta, residual)
         from . import parallel
         # under a HIP-graph capture the statistics exchange runs on the capture-only group, never on the
         # default group the eager warm-up steps used; the backward reuses the forward's choice
@@ -1269,13 +1274,9 @@ class _SyncBatchNormFn(torch.autograd.Function):
         allst = torch.zeros((world, 3 * C), device=x.device)
         call("srk_batchnorm_stats", ptr(x), M, C, ptr(allst[rank]), stream_ptr())
         dist.all_reduce(allst, op=dist.ReduceOp.SUM, group=group)
-        mean = torch.empty(C, device=x.device)
-        invstd = torch.empty(C, device=x.device)
         total = torch.empty(1, device=x.device)
         call("srk_batchnorm_combine", ptr(allst), world, C, float(eps), float(momentum), ptr(running_mean),
              ptr(running_var), ptr(mean), ptr(invstd), ptr(total), stream_ptr())
-        y = torch.empty_like(x)
-        res = residual.contiguous() if residual is not None else None
         call("srk_batchnorm_apply", ptr(x), M, C, ptr(mean), ptr(invstd), ptr(gamma), ptr(beta),
              _optr(res), int(relu), ptr(y), stream_ptr())
         ctx.save_for_backward(x, y, gamma, mean, invstd, total)
@@ -1288,20 +1289,16 @@ class _SyncBatchNormFn(torch.autograd.Function):
         import torch.distributed as dist
         x, y, gamma, mean, invstd, total = ctx.saved_tensors
         relu, has_res = ctx.flags
-        C = x.shape[-1]
-        M = x.numel() // C
-        dy = dy.contiguous()
+        dy, M, C, dx, dres = _bn_backward_buffers(ctx, dy, x, has_res)
         sums = torch.empty(2 * C, device=x.device)
         call("srk_batchnorm_bwd_reduce", ptr(x), ptr(y), ptr(dy), M, C, ptr(mean), ptr(invstd), relu, ptr(sums),
              stream_ptr())
         dbeta, dgamma = sums[:C].clone(), sums[C:].clone()     # this rank's contributions
         dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=ctx.group)
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        dres = torch.empty_like(x) if has_res and ctx.needs_input_grad[3] else None
         if dx is not None or dres is not None:
             call("srk_batchnorm_bwd_dx", ptr(x), ptr(y), ptr(dy), M, C, ptr(total), ptr(gamma), ptr(mean), ptr(invstd),
                  ptr(sums), relu, _optr(dx), _optr(dres), stream_ptr())
-        return dx, dgamma, dbeta, dres, None, None, None, None, None, None
+        return (dx, dgamma, dbeta, dres) + (None,) * 6
 
 
 class SyncBatchNorm1d(BatchNorm1d):
