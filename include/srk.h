@@ -693,6 +693,50 @@ int srk_dwconv2d_nhwc_bwd(const float* x, int64_t N, int64_t H, int64_t W, int64
 int srk_avgpool_nhwc_fwd(const float* x, int64_t N, int64_t HW, int64_t C, float* y, void* stream);
 int srk_avgpool_nhwc_bwd(const float* dy, int64_t N, int64_t HW, int64_t C, float* dx, void* stream);
 
+/* ---------------------------------------------------------------- transformer encoder pieces
+ * The three layers of a transformer encoder that are not a GEMM (nn.MultiheadSelfAttention, nn.LayerNorm, nn.GELU;
+ * the fbanks_kwt plugin; no reference counterpart).  All tensors fp32 and contiguous, fp32 arithmetic at every matmul
+ * precision.  Every sum has a fixed order and there are no floating-point atomics, so equal inputs give equal bits
+ * (eagerly and from a replayed graph).  Every launch is on the given stream, with no host synchronisation and no
+ * allocation.  Arguments are checked on the host before any device work: SRK_ERR_INVALID with the family's name
+ * ("mhsa", "layernorm", "gelu") in srk_last_error() for a null required pointer, a size outside the domain or a
+ * tensor of 2^31 elements or more.  A tensor whose base is not 16-byte aligned (or, LayerNorm, a D that is not a
+ * multiple of 4) takes scalar accesses instead of float4 ones.  Profiler categories "mhsa", "layernorm", "gelu": one
+ * record per call with its algorithmic bytes.
+ *
+ * Multi-head self-attention core (csrc/mhsa.hip), per clip b and head h:
+ *   S = scale Q K^T,  P = softmax over each row of S (row maximum subtracted),  O = P V.
+ * qkv [B][T][3 D], D = H dh, is the packed projection as a Linear writes it, torch's in_proj order: columns [0, D)
+ * q, [D, 2D) k, [2D, 3D) v, head h owning columns h dh .. (h + 1) dh - 1 of each third.  o [B][T][D] has the heads
+ * side by side.  The forward also writes lse [B][H][T], each row's log-sum-exp of S: all the backward keeps (P is
+ * recomputed as exp(S - lse); o is not read: rowsum(dO o O) = sum_j P_ij dP_ij).  The backward writes
+ * dqkv [B][T][3 D] in the packed layout: dV = P^T dO, dP = dO V^T, dS = P o (dP - rowsum(dO o O)),
+ * dQ = scale dS K, dK = scale dS^T Q.  Domain: B, H >= 1, 1 <= T <= 128, dh % 4 == 0, 4 <= dh <= 64, a finite scale,
+ * B T 3 D < 2^31.  No workspace.                                                                       */
+int srk_mhsa_fwd(const float* qkv, int64_t B, int64_t H, int64_t T, int64_t dh, float scale, float* o, float* lse,
+                 void* stream);
+int srk_mhsa_bwd(const float* qkv, const float* lse, const float* d_o, int64_t B, int64_t H, int64_t T, int64_t dh,
+                 float scale, float* dqkv, void* stream);
+/* LayerNorm over the last dimension of [M][D] (csrc/layernorm.hip):  s = x + res (res NULL: s = x),
+ *   y = (s - mean) rstd gamma + beta,  rstd = 1 / sqrt(var + eps), var the biased variance, computed as the mean of
+ * the centred squares after the mean.  mean and rstd [M] are saved for the backward, which recomputes s from x and
+ * res and writes ds [M][D] (the gradient of x and of res alike) and dgamma, dbeta [D]:
+ *   out = acc_beta * out + sum  (acc_beta 0: written without being read), the sum formed from per-workgroup partials
+ * in ws (srk_layernorm_workspace_floats floats, every word written before it is read) added in a fixed order (runs of
+ * consecutive partials in index order, then the runs in index order).
+ * Domain: M >= 1, 1 <= D <= 1024, M D < 2^31, eps finite and >= 0 (srk_layernorm_workspace_floats returns 0
+ * outside it).                                                                                          */
+int64_t srk_layernorm_workspace_floats(int64_t M, int64_t D);
+int srk_layernorm_fwd(const float* x, const float* res /* or NULL */, const float* gamma, const float* beta,
+                      int64_t M, int64_t D, float eps, float* y, float* mean, float* rstd, void* stream);
+int srk_layernorm_bwd(const float* x, const float* res /* or NULL */, const float* gamma, const float* mean,
+                      const float* rstd, const float* dy, int64_t M, int64_t D, float* ds, float* dgamma,
+                      float* dbeta, float acc_beta, float* ws, void* stream);
+/* GELU, erf form (csrc/gelu.hip; torch's default): y = x Phi(x), dx = dy (Phi(x) + x phi(x)), the backward reading
+ * x.  NaN propagates; every finite x gives finite y and dx.  1 <= n < 2^31.                            */
+int srk_gelu_fwd(const float* x, int64_t n, float* y, void* stream);
+int srk_gelu_bwd(const float* x, const float* dy, int64_t n, float* dx, void* stream);
+
 /* ---------------------------------------------------------------- SpecAugment on a feature map
  * Time warp, frequency masks and time masks (Park et al., Interspeech 2019) on a batch of feature clips, the
  * random draws made explicit and drawn on the device (features.spec_augment / specaug_draw; no reference

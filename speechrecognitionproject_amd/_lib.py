@@ -146,6 +146,13 @@ _SIGS = {
                               _I, _P],
     "srk_avgpool_nhwc_fwd": [_P, _I64, _I64, _I64, _P, _P],
     "srk_avgpool_nhwc_bwd": [_P, _I64, _I64, _I64, _P, _P],
+    "srk_mhsa_fwd": [_P, _I64, _I64, _I64, _I64, _F, _P, _P, _P],
+    "srk_mhsa_bwd": [_P, _P, _P, _I64, _I64, _I64, _I64, _F, _P, _P],
+    "srk_layernorm_workspace_floats": [_I64, _I64],
+    "srk_layernorm_fwd": [_P, _P, _P, _P, _I64, _I64, _F, _P, _P, _P, _P],
+    "srk_layernorm_bwd": [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _F, _P, _P],
+    "srk_gelu_fwd": [_P, _I64, _P, _P],
+    "srk_gelu_bwd": [_P, _P, _I64, _P, _P],
     "srk_specaug_apply": [_P, _I64, _I64, _I64, _I, _P, _I, _I, _I, _F, _P, _P],
     "srk_specaug_draw": [_P, _I64, _I64, _I64, _I, _I, _I, _I, _I, _P, _P],
     "srk_mixup_draw": [_P, _I64, _D, _P, _P, _P],
@@ -157,7 +164,7 @@ _RESTYPE = {"srk_last_error": ctypes.c_char_p, "srk_spin_timeouts": ctypes.c_int
             "srk_conv2d_workspace_floats": ctypes.c_int64, "srk_conv1_pool_workspace_floats": ctypes.c_int64,
             "srk_pitch_workspace_bytes": ctypes.c_int64, "srk_source_stamp": ctypes.c_char_p,
             "srk_pcen_workspace_floats": ctypes.c_int64, "srk_dwconv2d_workspace_floats": ctypes.c_int64,
-            "srk_adamw_workspace_floats": ctypes.c_int64}
+            "srk_adamw_workspace_floats": ctypes.c_int64, "srk_layernorm_workspace_floats": ctypes.c_int64}
 
 
 class SrkError(RuntimeError):

@@ -1016,6 +1016,219 @@ class GlobalAvgPool2d(tnn.Module):
         return _GlobalAvgPoolFn.apply(x)
 
 
+# ----------------------------------------------------------------------------- transformer encoder
+class _LayerNormFn(torch.autograd.Function):
+    """srk_layernorm_fwd / _bwd (include/srk.h): fp32 at every matmul precision, _BatchNormFn's conventions (dgamma /
+    dbeta ADDED into FlatParams-owned .grad by the launch that forms them).  One ds serves x and the residual."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, residual, eps):
+        x = x.contiguous()
+        res = None if residual is None else residual.contiguous()
+        _check_cuda(x, gamma, beta, res)
+        D = x.shape[-1]
+        if gamma.shape != (D,) or beta.shape != (D,) or (res is not None and res.shape != x.shape):
+            raise _lib.SrkError("LayerNorm: x [..., %d] needs gamma, beta [%d] and a residual of x's shape, got %s, %s, %s"
+                                % (D, D, tuple(gamma.shape), tuple(beta.shape), None if res is None else tuple(res.shape)))
+        M = x.numel() // max(D, 1)
+        y = torch.empty_like(x)
+        mean, rstd = torch.empty(M, device=x.device), torch.empty(M, device=x.device)
+        call("srk_layernorm_fwd", ptr(x), _optr(res), ptr(gamma), ptr(beta), M, D, float(eps), ptr(y), ptr(mean),
+             ptr(rstd), stream_ptr())
+        ctx.save_for_backward(x, res, gamma, mean, rstd)
+        ctx.params = (gamma, beta)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, res, gamma, mean, rstd = ctx.saved_tensors
+        D = x.shape[-1]
+        M = x.numel() // D
+        dy = dy.contiguous()
+        ds = torch.empty_like(x)
+        acc = _param_grad_target(ctx, ctx.params)
+        dgamma, dbeta = acc if acc else (torch.empty_like(gamma), torch.empty_like(gamma))
+        ws = torch.empty(int(_lib.lib().srk_layernorm_workspace_floats(M, D)), device=x.device)
+        call("srk_layernorm_bwd", ptr(x), _optr(res), ptr(gamma), ptr(mean), ptr(rstd), ptr(dy), M, D, ptr(ds),
+             ptr(dgamma), ptr(dbeta), 1.0 if acc else 0.0, ptr(ws), stream_ptr())
+        dres = ds if res is not None and ctx.needs_input_grad[3] else None
+        return (ds if ctx.needs_input_grad[0] else None, *_param_grad_done(ctx.params, (dgamma, dbeta), acc), dres,
+                None)
+
+
+class LayerNorm(tnn.Module):
+    """``nn.LayerNorm(D)`` parameters (weight, bias; ones / zeros) over the last dimension, 1 <= D <= 1024, with an
+    optional fused residual: ``forward(x, residual)`` normalises ``x + residual`` without writing the sum."""
+
+    def __init__(self, normalized_shape, eps=1e-5):
+        super().__init__()
+        self.normalized_shape, self.eps = (int(normalized_shape),), float(eps)
+        self.weight = tnn.Parameter(torch.ones(self.normalized_shape))
+        self.bias = tnn.Parameter(torch.zeros(self.normalized_shape))
+
+    def forward(self, x, residual=None):
+        require_gpu()
+        return _LayerNormFn.apply(x, self.weight, self.bias, residual, self.eps)
+
+
+class _GELUFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        _check_cuda(x)
+        y = torch.empty_like(x)
+        call("srk_gelu_fwd", ptr(x), x.numel(), ptr(y), stream_ptr())
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, = ctx.saved_tensors
+        dx = torch.empty_like(x)
+        call("srk_gelu_bwd", ptr(x), ptr(dy.contiguous()), x.numel(), ptr(dx), stream_ptr())
+        return dx
+
+
+class GELU(tnn.Module):
+    """``nn.GELU()`` (the erf form), one kernel each way; the backward reads x."""
+
+    def forward(self, x):
+        require_gpu()
+        return _GELUFn.apply(x)
+
+
+class _MHSAFn(torch.autograd.Function):
+    """srk_mhsa_fwd / _bwd on the packed projection qkv [B, T, 3 D] -> o [B, T, D]; fp32 at every matmul precision.
+    The row log-sum-exps are all the forward keeps besides qkv."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, scale):
+        qkv = qkv.contiguous()
+        _check_cuda(qkv)
+        if qkv.dim() != 3 or qkv.shape[2] % (3 * heads):
+            raise _lib.SrkError("self-attention: qkv must be [B, T, 3 * heads * dh], got %s with %d heads"
+                                % (tuple(qkv.shape), heads))
+        B, T, D3 = qkv.shape
+        D = D3 // 3
+        o = torch.empty((B, T, D), device=qkv.device)
+        lse = torch.empty((B, heads, T), device=qkv.device)
+        call("srk_mhsa_fwd", ptr(qkv), B, heads, T, D // heads, scale, ptr(o), ptr(lse), stream_ptr())
+        ctx.save_for_backward(qkv, lse)
+        ctx.consts = (heads, scale)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, lse = ctx.saved_tensors
+        heads, scale = ctx.consts
+        B, T, D3 = qkv.shape
+        dqkv = torch.empty_like(qkv)
+        call("srk_mhsa_bwd", ptr(qkv), ptr(lse), ptr(do.contiguous()), B, heads, T, D3 // (3 * heads), scale,
+             ptr(dqkv), stream_ptr())
+        return dqkv, None, None
+
+
+class MultiheadSelfAttention(tnn.Module):
+    """``nn.MultiheadAttention(embed_dim, num_heads, batch_first=True)`` called as ``attn(x, x, x)`` without mask or
+    dropout: the same parameter names, shapes and initial values (``in_proj_weight`` [3D, D], ``in_proj_bias`` [3D],
+    ``out_proj``), ``forward(x [B, T, D]) -> [B, T, D]``.  The in-projection writes q, k, v packed as one [B, T, 3D]
+    tensor that the attention core (srk_mhsa_*: T <= 128, head size a multiple of 4 in 4..64, scale head size ** -0.5)
+    reads in place; its output is the out-projection's input, heads side by side.  The two projections are GEMMs
+    and follow the matmul precision; the core is fp32."""
+
+    def __init__(self, embed_dim, num_heads):
+        super().__init__()
+        if embed_dim <= 0 or num_heads <= 0 or embed_dim % num_heads:
+            raise ValueError("embed_dim %r must be a positive multiple of num_heads %r" % (embed_dim, num_heads))
+        dh = embed_dim // num_heads
+        if dh % 4 or not 4 <= dh <= 64:
+            raise ValueError("head size %d is outside the attention kernel's domain (a multiple of 4 in 4..64)" % dh)
+        self.embed_dim, self.num_heads, self.head_dim = embed_dim, num_heads, dh
+
+        # torch's own initial values, drawn in torch's order (nn.MultiheadAttention: out_proj's Linear init first, then
+        # xavier_uniform_ on in_proj_weight and zero biases), so one seed gives the two modules equal parameters
+        self.in_proj_weight = tnn.Parameter(torch.empty(3 * embed_dim, embed_dim))
+        self.in_proj_bias = tnn.Parameter(torch.zeros(3 * embed_dim))
+        self.out_proj = Linear(embed_dim, embed_dim)
+        tnn.init.xavier_uniform_(self.in_proj_weight)
+        with torch.no_grad():
+            self.out_proj.bias.zero_()
+
+    def forward(self, x):
+        require_gpu()
+        if x.dim() != 3 or x.shape[2] != self.embed_dim:
+            raise _lib.SrkError("self-attention: x must be [B, T, %d], got %s" % (self.embed_dim, tuple(x.shape)))
+        B, T, D = x.shape
+        qkv = _LinearFn.apply(x.reshape(B * T, D), self.in_proj_weight, self.in_proj_bias).view(B, T, 3 * D)
+        o = _MHSAFn.apply(qkv, self.num_heads, self.head_dim ** -0.5)
+        return self.out_proj(o)
+
+
+class TransformerEncoderLayer(tnn.Module):
+    """``nn.TransformerEncoderLayer(d_model, nhead, dim_feedforward, dropout=0, activation='gelu', batch_first=True,
+    norm_first=False)``: post-norm, ``x = norm1(x + self_attn(x)); x = norm2(x + linear2(gelu(linear1(x))))``, with
+    torch's submodule names, shapes and initial values, so the two ``state_dict``s are interchangeable.  Both
+    residual adds run inside the LayerNorm kernels."""
+
+    def __init__(self, d_model, nhead, dim_feedforward):
+        super().__init__()
+        # torch's construction order, so one seed gives torch's initial values
+        self.self_attn = MultiheadSelfAttention(d_model, nhead)
+        self.linear1 = Linear(d_model, dim_feedforward)
+        self.linear2 = Linear(dim_feedforward, d_model)
+        self.norm1 = LayerNorm(d_model)
+        self.norm2 = LayerNorm(d_model)
+        self.gelu = GELU()
+
+    def forward(self, x):
+        x = self.norm1(self.self_attn(x), residual=x)
+        return self.norm2(self.linear2(self.gelu(self.linear1(x))), residual=x)
+
+
+class _EmbedPosFn(torch.autograd.Function):
+    """tokens = x W^T + b + pos for x [B T, K] and a table pos [T, N]: the table tiled over the batch is the C operand
+    of the GEMM and the add is its beta = 1 epilogue (srk_gemm_f32).  The backward is _LinearFn's, plus the table's
+    gradient: the column sums over the batch of dy viewed [B, T N] (srk_colsum_f32), added into a FlatParams-owned
+    .grad when there is one."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, pos):
+        x = x.contiguous()
+        _check_cuda(x, w, b, pos)
+        w_param = w
+        w = w.contiguous()
+        M, K = x.shape
+        T, N = pos.shape
+        if M % T or w.shape != (N, K):
+            raise _lib.SrkError("embedding: x [B * %d, K] needs a weight [%d, K], got %s and %s"
+                                % (T, N, tuple(x.shape), tuple(w.shape)))
+        y = pos.detach().repeat(M // T, 1)
+        call("srk_gemm_f32", 0, 1, M, N, K, 1.0, ptr(x), K, ptr(w), K, 1.0, ptr(y), N, _optr(b),
+             1 if b is not None else 0, stream_ptr())
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = b is not None
+        ctx.params = (w_param, b)
+        ctx.pos = pos
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = dy.contiguous()
+        pos = ctx.pos
+        dpos = None
+        if ctx.needs_input_grad[3]:
+            B, n = dy.shape[0] // pos.shape[0], pos.numel()
+            gp = _flat_grad(pos) if INPLACE_GRADS else None
+            dpos = gp if gp is not None else torch.empty_like(pos)
+            call("srk_colsum_f32", ptr(dy), B, n, n, ptr(dpos), 1.0 if gp is not None else 0.0, stream_ptr())
+            if gp is not None:
+                red = _reducer_of(pos)
+                if red is not None:
+                    red.mark_ready([pos])
+                dpos = None
+        return (*_LinearFn.backward(ctx, dy), dpos)
+
+
 _DROPOUT_STATE = {}   # device index -> int64[2] {base seed, call counter} read by srk_dropout_fwd_state
 _MASK63 = (1 << 63) - 1
 _DROPOUT_REPLAY = [0]

@@ -24,10 +24,11 @@ the device counter on top of the last eager seed, so masks (not the arithmetic) 
 ``--no-graph``.  ``--precision bf16|fp16`` runs the matrix cores on 16-bit operands (fp32
 accumulation, fp32 parameters); fp16 trains with a loss scale (``--loss-scale``: dynamic by
 default, or a fixed number) and skips any step whose gradients overflowed (optim.LossScaler).
-``--vtlp LO,HI`` (fbanks_cnn, fbanks_cnn_pcen and fbanks_dscnn, off by default) warps each training clip's mel filter bank by a
+``--vtlp LO,HI`` (fbanks_cnn, fbanks_cnn_pcen, fbanks_dscnn and fbanks_kwt, off by default) warps each training clip's mel filter bank by a
 factor drawn on the device (legacy/model_8/dataset_top.py:245-267); the draw's counter lives on the
 device too, so replayed and eager steps draw the same sequence.  ``--model fbanks_dscnn`` is the small-footprint
-depthwise-separable CNN on the same filter banks (models/model_fbanks_dscnn.py).
+depthwise-separable CNN on the same filter banks (models/model_fbanks_dscnn.py), ``--model fbanks_kwt`` the Keyword
+Transformer encoder on them (models/model_fbanks_kwt.py; no ``--specaug`` yet).
 ``--specaug W,NF,FMAX,NT,TMAX`` (the MFCC, filter-bank and spectrogram plugins of SPECAUG_SHAPES, off by default) runs
 SpecAugment on the feature map each training step reads: one frame moved by up to W frames with the rest stretched
 linearly around it, NF masks of up to FMAX features and NT masks of up to TMAX frames, filled with the clip's mean
@@ -63,7 +64,7 @@ from .nn import CrossEntropyLoss
 from .optim import Adam, FlatParams, LossScaler
 
 PLUGINS = ("mfcc_bgru", "fbanks_cnn", "spec_bgru", "resnet_bgru", "mfrn_bgru", "cnn_bgru", "spec_cnn", "resnet_dconv",
-           "mfcc_bgru_att", "fbanks_cnn_pcen", "fbanks_dscnn")
+           "mfcc_bgru_att", "fbanks_cnn_pcen", "fbanks_dscnn", "fbanks_kwt")
 # the plugins whose Network takes specaug=..., with the (frames, features) of the clips their networks read
 SPECAUG_SHAPES = {"mfcc_bgru": (51, 39), "mfcc_bgru_att": (51, 39), "fbanks_cnn": (98, 120), "fbanks_cnn_pcen": (98, 120),
                   "fbanks_dscnn": (98, 120), "spec_bgru": (49, 321), "spec_cnn": (49, 321)}
@@ -112,7 +113,7 @@ def parse(argv=None):
                    help="write model.state_dict() to OUTPUT/models/model_KEY.ckpt after training (the reference's "
                         "checkpoint path, training.py:104-107)")
     p.add_argument('--vtlp', default=None, metavar='LO,HI',
-                   help="fbanks_cnn, fbanks_cnn_pcen, fbanks_dscnn: warp each training clip's mel filter bank by a factor drawn uniformly from "
+                   help="fbanks_cnn, fbanks_cnn_pcen, fbanks_dscnn, fbanks_kwt: warp each training clip's mel filter bank by a factor drawn uniformly from "
                         "[LO, HI) (vocal-tract-length perturbation, the reference's legacy/model_8 trains with "
                         "0.9,1.1); off by default")
     p.add_argument('--specaug', default=None, metavar='W,NF,FMAX,NT,TMAX',
@@ -162,8 +163,8 @@ def parse(argv=None):
             p.error('--specaug takes W,NF,FMAX,NT,TMAX inside the domain of %s (%d frames x %d features): %s'
                     % ((args.model,) + SPECAUG_SHAPES[args.model] + (e,)))
     if args.vtlp is not None:
-        if args.model not in ('fbanks_cnn', 'fbanks_cnn_pcen', 'fbanks_dscnn'):
-            p.error('--vtlp applies to --model fbanks_cnn, fbanks_cnn_pcen and fbanks_dscnn only')
+        if args.model not in ('fbanks_cnn', 'fbanks_cnn_pcen', 'fbanks_dscnn', 'fbanks_kwt'):
+            p.error('--vtlp applies to --model fbanks_cnn, fbanks_cnn_pcen, fbanks_dscnn and fbanks_kwt only')
         try:
             lo, hi = (float(v) for v in args.vtlp.split(','))
         except ValueError:
